@@ -18,8 +18,8 @@ the generated rows (the first round(0.85 k) treated likely voters and control un
 voters dropped), N = 1e7 rows KEPT per GPU (``n_generated`` in the JSON: ~5.5e7 drawn),
 21 tutorial covariates + 479 extra nuisance covariates, generated directly in HBM
 (random-init equivalent: there is no dataset download). W is confounded with the vote
-history there. ``--also-rct 1`` (default) then measures the same step on the RCT panel
-(``--dgp rct``: W independent of X, every coordinate of the W path moves -- the path
+history there. ``--full`` with ``--also-rct 1`` (default) then measures the same step on the
+RCT panel (``--dgp rct``: W independent of X, every coordinate of the W path moves -- the path
 solver's worst case) and reports it under ``"rct"``.
 
 Timed step (the metric of record): ONE ``ate_dml`` call on the resident
@@ -41,13 +41,25 @@ Secondary, under ``repeated`` (world 1, ``--repeats 3``): ``ate_dml(repeats=3)``
 DISTINCT 5-fold partitions of 25 micro-segments from one Gram pass and one path launch,
 median-aggregated (Chernozhukov et al. 2018 §3.4); the JSON lists the split ATEs.
 
-Parity (``--parity 1``, untimed): the same kept rows as a float64 panel, fp64 Gram and
+Parity (``--full``, ``--parity 1``, untimed): the same kept rows as a float64 panel, fp64 Gram and
 fp64 path solves; the JSON reports |dATE| / SE_f64 and the relative SE difference.
 
 Scaling: weak by default (N=1e7 rows per GPU; at N=1 GPU this is exactly the
 BASELINE config); ``--scaling strong`` keeps N=1e7 in total.
 
-    python bench.py --gpus N --steps K --warmup W
+A plain run does only what the headline needs: it generates the ``--dgp`` panel, captures
+the call, runs W warm-up and K timed steps, writes ``--dump-outputs`` and prints the
+result line. Every other block above -- ``single_fit_ms``, ``throughput_inflight``,
+``repeated``, ``parity``, ``rct`` -- takes runs of its own and is measured only with
+``--full`` (there ``--inflight`` / ``--repeats`` / ``--parity`` / ``--also-rct`` switch the
+blocks as described); without it those keys are null.
+
+``--dump-outputs DIR``: after the timed steps, what the last timed call returned is written
+as ``DIR/<name>.npy`` (float64 / float32; :func:`collect_outputs`). Panel and fold
+assignment depend on the arguments alone, so two builds run with the same arguments can
+be compared array for array.
+
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 """
 from __future__ import annotations
@@ -82,14 +94,14 @@ def parse():
                     help="tutorial: the selection-biased df_mod at scale (default); rct: W "
                          "independent of X (the path solver's worst case)")
     ap.add_argument("--also-rct", type=int, default=1,
-                    help="after the --dgp tutorial measurement, time the same step on the RCT "
-                         "panel too (JSON key 'rct')")
+                    help="--full: after the --dgp tutorial measurement, time the same step on "
+                         "the RCT panel too (JSON key 'rct')")
     # weak (default): every GPU holds N=1e7 rows of the named config, so N=1 is exactly
     # the BASELINE config and rows/s measures the data-parallel design. The CV-LASSO
     # path solve is O(p^2 * lambdas) and independent of N, so at a fixed total N it is
     # an Amdahl term every rank repeats (use --scaling strong to measure that).
     ap.add_argument("--repeats", type=int, default=3,
-                    help="> 1 (world 1): also time ate_dml(repeats=S) -- S distinct K-fold "
+                    help="--full, > 1 (world 1): also time ate_dml(repeats=S) -- S distinct K-fold "
                          "partitions of K*K micro-segments from one Gram pass, median-aggregated "
                          "(JSON key 'repeated'; secondary, not the metric of record)")
     ap.add_argument("--scaling", default="weak", choices=["strong", "weak"])
@@ -98,8 +110,9 @@ def parse():
                     help="capture the step in hipGraphs (default: on with a GPU; RCCL "
                          "collectives are captured inside them)")
     ap.add_argument("--parity", type=int, default=1,
-                    help="after the timed steps, fit the same rows from a float64 panel (fp64 "
-                         "Gram, fp64 path solves; untimed) and report the ATE / SE differences")
+                    help="--full: after the timed steps, fit the same rows from a float64 panel "
+                         "(fp64 Gram, fp64 path solves; untimed) and report the ATE / SE "
+                         "differences")
     ap.add_argument("--blocked", type=int, default=1,
                     help="1: 64-row blocked panel layout (one contiguous HBM run per Gram "
                          "K-step, ops/panel.py); 0: column-major")
@@ -108,9 +121,53 @@ def parse():
                          "shards, int64-limb Gram all-reduce, exact score moments: the same "
                          "ATE / SE bits at every world size; estimators/lasso.dml_phases)")
     ap.add_argument("--inflight", type=int, default=-1,
-                    help="secondary throughput block: identical cross-fits in flight (one "
+                    help="--full: secondary throughput block, identical cross-fits in flight (one "
                          "hipGraph + stream + Gram workspace each); 1 = skip")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary blocks (single-call latency, fits in "
+                         "flight, repeated cross-fitting, float64 parity, the RCT panel); a "
+                         "plain run times the --steps calls only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call returned as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+# --dump-outputs writes at most this many bytes in all; a larger array is cut to a fixed,
+# seeded sample of its entries
+DUMP_BYTES = 64 << 20
+
+
+def collect_outputs(st):
+    """Host copies of what the timed call hands its caller (estimators/lasso.
+    dml_crossfit_panel: ``res`` = [ATE, SE], the 7 score moments ``mom``, the CV fit's
+    lambda.min / lambda.1se coefficients of this rank's outer folds) and the fold Gram stack
+    they were solved from, as float32 (bf16 / f32 tensors) or float64 arrays by name."""
+    import numpy as np
+    import torch
+    cv = st.get("cv")
+    named = {"res": st.get("res"), "mom": st.get("mom"), "gram": st.get("G"),
+             "coef_min": getattr(cv, "coef_min", None), "coef_1se": getattr(cv, "coef_1se", None)}
+    named = {k: t for k, t in named.items() if isinstance(t, torch.Tensor)}
+    out = {}
+    for k, t in named.items():
+        t = t.detach().cpu()
+        a = t.to(torch.float32 if t.dtype in (torch.float32, torch.bfloat16, torch.float16)
+                 else torch.float64).numpy().copy()
+        keep = DUMP_BYTES // len(named) // a.itemsize
+        if a.size > keep:
+            a = a.ravel()[np.sort(np.random.RandomState(0).randint(0, a.size, keep))]
+        out[k] = a
+    return out
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def measure_inflight(args, comm, device, pan, inflight, fit_phases, agree, slot_comms_cache,
@@ -247,10 +304,11 @@ def pan_rows(pan, comm):
     return float(np.asarray(global_seg_counts(pan, comm)).sum())
 
 
-def measure(args, comm, device, dgp, n_total, slot_comms_cache):
+def measure(args, comm, device, dgp, n_total, slot_comms_cache, dump=None):
     """Build the ``dgp`` panel, capture one ate_dml call, time ``args.steps`` calls back to
-    back (the metric of record) and the median single-call latency, then the secondary
-    in-flight throughput. Returns a dict (and the panel, for the parity refit)."""
+    back (the metric of record) and write the last call's outputs to ``dump``; with
+    ``--full`` then the median single-call latency and the secondary in-flight throughput.
+    Returns a dict (and the panel, for the parity refit)."""
     import torch
     from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
     from ate_replication_causalml_amd.estimators.lasso import (EXACT_BLOCK, dml_phases,
@@ -330,11 +388,12 @@ def measure(args, comm, device, dgp, n_total, slot_comms_cache):
     sync()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        res = single()["res"]
+        st = single()
     sync()
     comm.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    res = st["res"]
     el = torch.tensor([elapsed], dtype=torch.float64, device=device)
     comm.all_reduce_max_(el)
     elapsed = float(el.item())
@@ -343,31 +402,36 @@ def measure(args, comm, device, dgp, n_total, slot_comms_cache):
         from ate_replication_causalml_amd.utils.guards import NumericalError
         raise NumericalError(f"bench step returned ate={ate} se={se} (truncated CV fold path?)")
     ms = elapsed / args.steps * 1e3
+    if dump and rank == 0:
+        write_outputs(dump, collect_outputs(st))
+    del st
     # latency of one call alone, each replay bracketed by device syncs (and a barrier):
     # median of >= 5 replays, the slowest rank per replay
-    nlat = max(5, min(args.steps, 11))
-    lats = []
-    for k in range(nlat):
-        sync()
-        comm.barrier()
-        t1 = time.perf_counter()
-        single()
-        sync()
-        lats.append(time.perf_counter() - t1)
-    lat_t = torch.tensor(lats, dtype=torch.float64, device=device)
-    comm.all_reduce_max_(lat_t)
-    lats = sorted(float(v) for v in lat_t.cpu())
-    lat = lats[len(lats) // 2]
+    lat, lats = None, []
+    if args.full:
+        nlat = max(5, min(args.steps, 11))
+        for k in range(nlat):
+            sync()
+            comm.barrier()
+            t1 = time.perf_counter()
+            single()
+            sync()
+            lats.append(time.perf_counter() - t1)
+        lat_t = torch.tensor(lats, dtype=torch.float64, device=device)
+        comm.all_reduce_max_(lat_t)
+        lats = sorted(float(v) for v in lat_t.cpu())
+        lat = lats[len(lats) // 2]
 
     inflight = 3 if args.inflight < 0 else max(1, args.inflight)
     inflight_out = None
-    if inflight > 1 and device.type == "cuda" and graphed:
+    if args.full and inflight > 1 and device.type == "cuda" and graphed:
         inflight_out = measure_inflight(args, comm, device, pan, inflight, fit_phases, agree,
                                         slot_comms_cache, sync, single)
     out = {
         "dgp": dgp, "ms_per_step": ms, "rows_per_s": n_total / (ms / 1e3),
-        "single_fit_ms": lat * 1e3, "single_fit_ms_all": [round(v * 1e3, 4) for v in lats],
-        "single_fit_rows_per_s": n_total / lat,
+        "single_fit_ms": lat and lat * 1e3,
+        "single_fit_ms_all": [round(v * 1e3, 4) for v in lats] if lats else None,
+        "single_fit_rows_per_s": lat and n_total / lat,
         "ate": ate, "se": se, "ate_hex": ate.hex(), "se_hex": se.hex(),
         "n_kept": n_total, "n_generated": int(pan.n_generated) * 1,
         "panel_gen_s": t_gen, "hipgraph": graphed, "graphs_per_fit": graphs_per_fit,
@@ -457,9 +521,10 @@ def main():
                                "bench step") if world > 1 else contextlib.nullcontext()
     guard.__enter__()
     cache = {}
-    main_m, pan, seg_counts = measure(args, comm, device, args.dgp, n_total, cache)
+    main_m, pan, seg_counts = measure(args, comm, device, args.dgp, n_total, cache,
+                                      dump=args.dump_outputs)
     parity = None
-    if args.parity and args.dtype != "f64":
+    if args.full and args.parity and args.dtype != "f64":
         # ATE/SE parity (the metric's second half), untimed: the same kept rows generated as
         # a float64 panel (the selection plan is reused: same rows), fp64 Gram and fp64 path
         # solves (the path tests/test_gpu.py pins against the float64 reference estimator)
@@ -484,13 +549,13 @@ def main():
         del pan64
         clear_plans()
     repeated = None
-    if args.repeats > 1 and world == 1 and not emulate:
+    if args.full and args.repeats > 1 and world == 1 and not emulate:
         clear_plans()
         repeated = measure_repeated(args, comm, device, n_total, pan.selection)
         clear_plans()
     del pan
     rct = None
-    if args.also_rct and args.dgp != "rct":
+    if args.full and args.also_rct and args.dgp != "rct":
         clear_plans()
         if device.type == "cuda":
             torch.cuda.empty_cache()
@@ -543,6 +608,7 @@ def main():
             "single_fit_rows_per_s": main_m["single_fit_rows_per_s"],
             "graphs_per_fit": main_m["graphs_per_fit"],
             "exact": bool(args.exact),
+            "full": bool(args.full),
             "collectives_captured": main_m["collectives_captured"],
             "panel_gen_s": main_m["panel_gen_s"],
             "throughput_inflight": main_m["inflight"],

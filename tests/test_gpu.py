@@ -464,7 +464,8 @@ def test_bench_eager_gram_matches_graph_gram(gpu):
     for eg in ("0", "1"):
         env = dict(os.environ, ATE_BENCH_EAGER_GRAM=eg)
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rows", "1e6",
-                            "--steps", "2", "--warmup", "1", "--parity", "0", "--also-rct", "0"],
+                            "--steps", "2", "--warmup", "1", "--full", "--parity", "0",
+                            "--also-rct", "0"],
                            capture_output=True, text=True, env=env, timeout=200)
         assert r.returncode == 0, r.stderr[-2000:]
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

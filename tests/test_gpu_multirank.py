@@ -19,7 +19,7 @@ def _json(out):
 
 def test_two_ranks_on_one_gpu_match_one_process(gpu):
     bench = os.path.join(ROOT, "bench.py")
-    args = ["--steps", "3", "--warmup", "1", "--parity", "0", "--also-rct", "0"]
+    args = ["--steps", "3", "--warmup", "1", "--full", "--parity", "0", "--also-rct", "0"]
     env = dict(os.environ, ATE_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node=2", "--master-addr=127.0.0.1", "--master-port=29655",

@@ -9,6 +9,6 @@ ms() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitli
 for i in $(seq ${1:-2}); do
   timeout -k 10 200 python $R/tools/enet_only.py 10 | sed 's/^/new  /' || exit 1
   ATE_HIP_LIB=$BASE timeout -k 10 200 python $R/tools/enet_only.py 10 | sed 's/^/base /' || exit 1
-  timeout -k 10 300 python $R/bench.py --steps 10 --warmup 3 | ms new || exit 1
-  ATE_HIP_LIB=$BASE timeout -k 10 300 python $R/bench.py --steps 10 --warmup 3 | ms base || exit 1
+  timeout -k 10 300 python $R/bench.py --steps 10 --warmup 3 --full | ms new || exit 1
+  ATE_HIP_LIB=$BASE timeout -k 10 300 python $R/bench.py --steps 10 --warmup 3 --full | ms base || exit 1
 done

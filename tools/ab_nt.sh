@@ -7,6 +7,6 @@ ms() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitli
 for i in 1 2; do
   timeout -k 10 200 python $R/tools/gram_only.py 1e7 | sed 's/^/base /' || exit 1
   ATE_HIP_LIB=$V timeout -k 10 200 python $R/tools/gram_only.py 1e7 | sed 's/^/nt   /' || exit 1
-  timeout -k 10 300 python $R/bench.py --steps 20 --warmup 3 | ms base || exit 1
-  ATE_HIP_LIB=$V timeout -k 10 300 python $R/bench.py --steps 20 --warmup 3 | ms nt || exit 1
+  timeout -k 10 300 python $R/bench.py --steps 20 --warmup 3 --full | ms base || exit 1
+  ATE_HIP_LIB=$V timeout -k 10 300 python $R/bench.py --steps 20 --warmup 3 --full | ms nt || exit 1
 done

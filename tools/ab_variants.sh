@@ -8,7 +8,7 @@ timeout -k 10 200 python $R/tools/enet_only.py 10 | sed 's/^/new  /' || exit 1
 for v in "$@"; do
   ATE_HIP_LIB=$R/ate_replication_causalml_amd/_lib/libatehip_$v.so timeout -k 10 200 python $R/tools/enet_only.py 10 | sed "s/^/$v /" || exit 1
 done
-timeout -k 10 300 python $R/bench.py --steps 10 --warmup 3 | ms new || exit 1
+timeout -k 10 300 python $R/bench.py --steps 10 --warmup 3 --full | ms new || exit 1
 for v in "$@"; do
-  ATE_HIP_LIB=$R/ate_replication_causalml_amd/_lib/libatehip_$v.so timeout -k 10 300 python $R/bench.py --steps 10 --warmup 3 | ms $v || exit 1
+  ATE_HIP_LIB=$R/ate_replication_causalml_amd/_lib/libatehip_$v.so timeout -k 10 300 python $R/bench.py --steps 10 --warmup 3 --full | ms $v || exit 1
 done

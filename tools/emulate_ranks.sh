@@ -3,6 +3,7 @@
 # shard of W x 1e7 rows, its outer folds' path solves, no-op collectives): projects the
 # per-rank step time of the multi-GPU runs without the RCCL cost.
 set -o pipefail
+BARGS="--full $BARGS"   # single_fit_ms below is one of bench.py's --full blocks
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out
 for w in ${WORLDS:-1 2 4 8}; do

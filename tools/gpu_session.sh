@@ -71,7 +71,7 @@ for step in "$@"; do
       done ;;
     prof)
       ( cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d "$ROOT/$OUT/prof" -o bench -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --also-rct 0 \
+          -d "$ROOT/$OUT/prof" -o bench -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --full --also-rct 0 \
           > "$ROOT/$OUT/prof.log" 2>&1 ) || { echo "[prof] failed"; tail -20 "$OUT/prof.log"; exit 1; }
       python3 -c "import sys; sys.path.insert(0, 'tools'); import timeline; timeline.overlapped(sys.argv[1], 24)" \
           $(find "$OUT/prof" -name "*kernel_trace.csv") > "$OUT/prof_timeline.txt" 2>&1 || true
@@ -136,7 +136,7 @@ for step in "$@"; do
       ENGINES=level run lvplain 200 python -u tools/forest_level_probe.py ;;
     single)      # kernel trace of bench.py: the last single-fit replay's critical path
       ( cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv \
-          -d "$ROOT/$OUT/single" -o single -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 \
+          -d "$ROOT/$OUT/single" -o single -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --full \
           --parity 0 --also-rct 0 --dgp "${ATE_DGP:-tutorial}" > "$ROOT/$OUT/single_run.log" 2>&1 ) || { echo "[single] failed"; tail -20 "$OUT/single_run.log"; exit 1; }
       python3 tools/single_fit_timeline.py $(find "$OUT/single" -name "*kernel_trace.csv") \
           > "$OUT/single_timeline.txt" 2>&1

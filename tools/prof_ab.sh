@@ -12,6 +12,6 @@ for nm in "${libs[@]}"; do
   [ "$nm" = new ] && lib=$ROOT/ate_replication_causalml_amd/_lib/libatehip.so
   ( cd /tmp && export TMPDIR=/tmp ATE_HIP_LIB=$lib && timeout -k 10 300 rocprofv3 --kernel-trace \
       --stats --output-format csv -d "$OUT/prof_$nm" -o bench -- python3 "$ROOT/bench.py" \
-      --steps 5 --warmup 1 --parity 0 > "$OUT/prof_$nm.log" 2>&1 ) || { echo "[$nm] failed"; exit 1; }
+      --steps 5 --warmup 1 --full --parity 0 > "$OUT/prof_$nm.log" 2>&1 ) || { echo "[$nm] failed"; exit 1; }
   echo "[$nm] ok"
 done

@@ -2,6 +2,7 @@
 # Kernel trace of a bench run (extra args in BARGS, env passed through) + tools/timeline.py
 # listing of its overlapped part -> gpurun_out/prof_tl/timeline.txt
 set -o pipefail
+BARGS="--full $BARGS"   # the overlapped fits are bench.py's --full in-flight block
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out/prof_tl
 cd /tmp

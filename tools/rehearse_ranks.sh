@@ -8,7 +8,7 @@ mkdir -p $R/gpurun_out
 ROWS=${ROWS:-2000000}
 for W in ${WORLDS:-2 3}; do
   ATE_DIST_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W \
-    --master-addr 127.0.0.1 --master-port $((29600 + W)) $R/bench.py --gpus $W --rows $ROWS --steps 5 --warmup 2 --parity 0 \
+    --master-addr 127.0.0.1 --master-port $((29600 + W)) $R/bench.py --gpus $W --rows $ROWS --steps 5 --warmup 2 --full --parity 0 \
     > $R/gpurun_out/rehearse_$W.log 2>&1 || { echo "world $W failed"; tail -20 $R/gpurun_out/rehearse_$W.log; exit 1; }
   timeout -k 10 300 python $R/bench.py --rows $((ROWS * W)) --steps 2 --warmup 1 --parity 0 > $R/gpurun_out/rehearse_1x$W.log 2>&1 || exit 1
   python - $R/gpurun_out/rehearse_$W.log $R/gpurun_out/rehearse_1x$W.log $W <<'PY'

@@ -1,4 +1,4 @@
-"""Kernel sequence of the LAST single-fit replay in a kernel trace of ``bench.py --parity 0``
+"""Kernel sequence of the LAST single-fit replay in a kernel trace of ``bench.py --full --parity 0``
 (the latency replays run last): every kernel from the replay's first kernel to its last,
 with start offset, duration and the idle gap before it; then the replay's wall, busy time
 and the sums per kernel class. Shows what sits on the single call's critical path.
