@@ -98,6 +98,7 @@ _SIGS = {
     "ate_enet_pick": "ppiiipppip",
     "ate_dml_resid_moments": "ipllpipipiiiiiippp",
     "ate_dml_resid_exact": "pllpipipiiiiiiippp",
+    "ate_irm_score_moments": "ipllpipiipiiiiidippp",
     "ate_lognet_path": "iplpiipipipdddippippppppppp",
     "ate_lognet_cvloss": "iplpiippipppipp",
     "ate_dgp_fill": "iplllllp" + "uiipppp",

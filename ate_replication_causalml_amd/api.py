@@ -16,7 +16,8 @@ prop_score_ols -> ate_ipw_wls; ate_condmean_lasso -> ate_lasso_single; ate_lasso
 ate_lasso; prop_score_lasso -> propensity_lasso; doubly_robust -> ate_aipw_rf;
 doubly_robust_glm -> ate_aipw_glm; belloni -> ate_belloni; double_ml ->
 ate_double_ml; residual_balance_ATE -> ate_residual_balance; grf::causal_forest +
-estimate_average_effect -> ate_causal_forest; K-fold DML-PLR -> ate_dml.
+estimate_average_effect -> ate_causal_forest; K-fold DML-PLR -> ate_dml; K-fold DML-IRM
+(cross-fitted AIPW, LASSO nuisances) -> ate_dml_irm.
 """
 from __future__ import annotations
 
@@ -230,6 +231,23 @@ def ate_dml(Y, W, X, folds=5, lambda_rule="min", method="DML cross-fit (LASSO)",
                                 method=method, device=run.device(), dtype=run.dtype)
 
 
+def ate_dml_irm(Y, W, X, folds=5, lambda_rule="min", clip=0.01,
+                method="DML-IRM cross-fit (LASSO)", run=None) -> AteResult:
+    """K-fold cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1)
+    with CV-LASSO nuisances: per-arm outcome regressions and the linear-probability
+    propensity (clipped to [clip, 1 - clip]) on the fold Gram stack; the ATE under
+    heterogeneous effects, doubly robust (estimators/irm.py). W must be binary."""
+    run = _run(run)
+    with trace("ate_dml_irm", folds=folds):
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_irm_lasso(Y, W, X, folds=folds, seed=run.seed, lambda_rule=lambda_rule,
+                                   clip=clip, method=method)
+        from .estimators import irm as DI
+        return DI.dml_irm_lasso(Y, W, X, folds=folds, seed=run.seed, lambda_rule=lambda_rule,
+                                clip=clip, method=method, device=run.device(), dtype=run.dtype)
+
+
 def ate_residual_balance(Y, W, X, balance: BalanceConfig | None = None,
                          method="residual_balancing", run=None) -> AteResult:
     """E14 residual_balance_ATE (ate_functions.R:393-405) -> balanceHD::residualBalance.ate."""
@@ -403,7 +421,7 @@ def replicate(data=None, config: ReplicateConfig | None = None, log_path=None, p
 __all__ = [
     "ate_naive", "ate_ols", "propensity_logistic", "propensity_lasso", "ate_ipw", "ate_ipw_wls",
     "ate_lasso_single", "ate_lasso", "ate_aipw_rf", "ate_aipw_glm", "ate_belloni",
-    "ate_double_ml", "ate_dml", "ate_residual_balance", "ate_causal_forest", "replicate",
+    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_residual_balance", "ate_causal_forest", "replicate",
     "ate_aipw_crossfit", "ate_causal_forest_bootstrap",
     "Replication", "AteResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
 ]

@@ -41,7 +41,18 @@ def _dml(a):
     from .estimators.lasso import dml_crossfit_panel, dml_repeated_panel
     from .estimators.common import read_result
     dev = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
-    if a.repeats > 1:
+    if a.model == "irm":
+        # interactive model: arm-split panel (segment 2k + a = fold k, W = a), AIPW score
+        from .estimators.irm import irm_crossfit_panel
+        if a.repeats > 1:
+            raise SystemExit("--model irm has no repeated cross-fitting")
+        pan = synthetic_panel(a.n, p=a.p, folds=a.folds, seed=a.seed, dtype=a.dtype, device=dev,
+                              arm_split=True)
+        res, mom, cv = irm_crossfit_panel(pan, a.folds, a.lambda_rule, a.clip)
+        r = read_result(res, "DML-IRM cross-fit (LASSO)", n=a.n)
+        out = {"ate": r.ate, "se": r.se, "lower_ci": r.lower_ci, "upper_ci": r.upper_ci,
+               "n_clipped": int(round(float(mom[3])))}
+    elif a.repeats > 1:
         # repeated cross-fitting: K*K micro-segments, `repeats` distinct K-fold partitions
         pan = synthetic_panel(a.n, p=a.p, folds=a.folds * a.folds, seed=a.seed, dtype=a.dtype,
                               device=dev)
@@ -98,6 +109,10 @@ def main(argv=None):
     d.add_argument("--repeats", type=int, default=1,
                    help="> 1: repeated cross-fitting over that many distinct K-fold partitions")
     d.add_argument("--aggregate", default="median", choices=["median", "mean"])
+    d.add_argument("--model", default="plr", choices=["plr", "irm"],
+                   help="plr: partially linear model; irm: interactive model (cross-fitted AIPW)")
+    d.add_argument("--clip", type=float, default=0.01,
+                   help="irm: the propensity is clipped to [clip, 1 - clip]")
     d.set_defaults(fn=_dml)
     b = sub.add_parser("build")
     b.set_defaults(fn=_build)

@@ -86,10 +86,34 @@ def byte_column_order(names: list, p: int, P: int):
     return cont + [nm for nm in names if nm in binary]
 
 
+def _arm_split_ids(base: DevicePanel):
+    """Stable partition of every segment's rows of the unsplit panel ``base`` by arm:
+    (rows per segment 2k + a, their generated-row ids concatenated in segment order, their
+    global row ids per segment, the selection plan)."""
+    w = base.col("W").double()
+    counts, gparts, rows = [], [], []
+    off = 0
+    for (r0, _), cnt in zip(base.seg_bounds, base.seg_nreal):
+        r0, cnt = int(r0), int(cnt)
+        wk = w[r0:r0 + cnt]
+        rk = base.row_index[r0:r0 + cnt]
+        gk = rk if base.gen_ids is None else base.gen_ids[off:off + cnt]
+        off += cnt
+        for a in (0, 1):
+            ix = torch.nonzero(wk == a).reshape(-1)     # ascending: the fold's own order
+            counts.append(int(ix.numel()))
+            gparts.append(gk[ix])
+            rows.append(rk[ix])
+    if sum(counts) != base.n:
+        raise ValueError("arm_split needs a binary W column")
+    return counts, torch.cat(gparts).contiguous(), rows, base.selection
+
+
 def synthetic_panel(n_total: int, p: int = 500, folds: int = 5, seed: int = 1991,
                     dtype: str = "bf16", device="cpu", rank: int = 0, world: int = 1,
                     blocked: bool = False, align: int = 0, dgp: str = "rct", comm=None,
-                    selection=None, compat: str = "reference") -> DevicePanel:
+                    selection=None, compat: str = "reference",
+                    arm_split: bool = False) -> DevicePanel:
     """``align`` > 0: block-aligned rank slices (fold_slices); the panel then records
     ``exact_block`` = align, the row block of the exact (world-size-invariant) Gram.
 
@@ -97,7 +121,13 @@ def synthetic_panel(n_total: int, p: int = 500, folds: int = 5, seed: int = 1991
     shards its candidate counting over the ranks (one all-reduce of per-block counts);
     ``selection``: a PanelSelection already planned for these (n_total, seed) (e.g. by the
     bf16 panel, reused for its float64 parity twin). The panel records ``dgp``,
-    ``n_generated`` and ``selection``."""
+    ``n_generated`` and ``selection``.
+
+    ``arm_split``: a 2 * folds segment panel, segment ``2k + a`` = the rows of fold k with
+    W = a in their fold order (the layout of estimators/irm.py): the same rows with bit for
+    bit the same values as the unsplit panel, only their order changes. The unsplit panel is
+    generated first and its W column read (set-up work, not part of any timed call); each
+    rank splits its own slices. Not combined with ``align``."""
     if p < N_TUTORIAL_COLS:
         raise ValueError("p must be >= 21 (tutorial columns)")
     if dgp not in DGPS:
@@ -106,7 +136,15 @@ def synthetic_panel(n_total: int, p: int = 500, folds: int = 5, seed: int = 1991
         rank, world = comm.rank, comm.world_size
     p_extra = p - N_TUTORIAL_COLS
     params = host_dgp.PANEL if dgp == "rct" else host_dgp.TUTORIAL
+    if arm_split and align:
+        raise ValueError("arm_split panels are not block-aligned: align must be 0")
     slices = fold_slices(n_total, folds, rank, world, align)
+    split = None
+    if arm_split:
+        split = _arm_split_ids(synthetic_panel(
+            n_total, p=p, folds=folds, seed=seed, dtype=dtype, device=device, rank=rank,
+            world=world, blocked=blocked, dgp=dgp, comm=comm, selection=selection, compat=compat))
+        slices = [(0, c) for c in split[0]]     # every row's id is explicit (split[1])
     hi_lo = dtype == "bf16"
     names = ["one"] + [f"x{j}" for j in range(p)] + ["W", "Y"]
     if hi_lo:
@@ -132,7 +170,11 @@ def synthetic_panel(n_total: int, p: int = 500, folds: int = 5, seed: int = 1991
     pan.identity = len(slices) == 1 and slices[0][0] == 0
     gids = None
     sel = None
-    if dgp == "tutorial":
+    if split is not None:
+        _, gids, rows, sel = split
+        for k, (r0, _) in enumerate(pan.seg_bounds):
+            rid[r0:r0 + int(split[0][k])] = rows[k]
+    elif dgp == "tutorial":
         from .panel_selection import kept_gids, plan_selection
         pcomm = None if getattr(comm, "emulated", False) else comm   # --shard r/W: plan alone
         sel = selection if selection is not None else plan_selection(

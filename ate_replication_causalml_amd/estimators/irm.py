@@ -1,0 +1,268 @@
+"""Cross-fitted AIPW for the interactive regression model (DML-IRM, Chernozhukov et al.
+2018 §5.1) with CV-LASSO nuisances on the fold Gram stack.
+
+Where ``lasso.dml_plr_lasso`` estimates the one coefficient of the partially linear model
+(the ATE only under a constant effect), this estimator fits the outcome regression per arm,
+g0(X) = E[Y|X, W=0] and g1(X) = E[Y|X, W=1], and the linear-probability propensity
+m(X) = E[W|X], all by gaussian CV-LASSO, and averages the doubly robust score
+
+    psi = g1 - g0 + w (y - g1) / m - (1 - w)(y - g0) / (1 - m),   m clipped to [clip, 1-clip]
+
+over held-out rows (textbook signs, as ``crossfit.aipw_score``).
+
+Layout: a 2K-segment panel, segment ``2k + a`` = the rows of fold k with W = a. One Gram
+pass (K01) then yields per-(fold, arm) Grams; the fold Grams of the propensity problems are
+their pairwise sums. All 3 K (K + 1) path problems (3 nuisances x K outer folds x (1 full +
+K - 1 inner CV)) run in ONE ``ate_enet_path`` launch (``ops/enet.cv_enet_gaussian(full_y=)``),
+and one fused pass over the panel (csrc/irm.hip) accumulates the 8 score moments.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _native
+from ..ops.devconst import const
+from ..ops.enet import cv_enet_gaussian
+from ..ops.gram import gram
+from ..ops.panel import build_panel, dtype_code
+from ..result import AteResult
+from ..utils.graphs import estimator_graphs
+from .common import as_np, resolve_device
+from .lasso import _fold_ids, _tri_index, allreduce_sym_, global_seg_counts
+
+N_MOMENTS = 8   # [S psi, S psi^2, n, n_clipped, S w(y-g1)^2, S (1-w)(y-g0)^2, S (w-m)^2, n_treated]
+
+
+def _yw_columns(pan):
+    """(y0, y1, w0, w1): the target columns the score pass reads; bf16 panels carry Y / W
+    as hi + lo pairs (exact for binary targets), the others as one column (second = -1)."""
+    if pan.dtype == torch.bfloat16:
+        return pan.cols["Y_hi"], pan.cols["Y_lo"], pan.cols["W_hi"], pan.cols["W_lo"]
+    return pan.cols["Y"], -1, pan.cols["W"], -1
+
+
+def irm_score_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
+                      nbx: int | None = None) -> torch.Tensor:
+    """Fused held-out AIPW score pass -> the 8 fp64 moments (N_MOMENTS).
+
+    coef: [nfold, 3, p+1] fp64, rows (g0, g1, m), intercept first; segment s of the panel
+    uses block ``s // segs_per_fold`` (2: the arm-split layout; 1: a plain K-fold panel).
+    W is read from the panel on every row. GPU: csrc/irm.hip (``nbx`` blocks per segment);
+    CPU: the float64 torch twin below, the kernel's oracle."""
+    nseg = pan.nseg
+    nfold = coef.shape[0]
+    if segs_per_fold < 1 or nfold * segs_per_fold < nseg:
+        raise ValueError(f"{nseg} segments at {segs_per_fold} per fold need "
+                         f"{-(-nseg // max(segs_per_fold, 1))} coefficient blocks, got {nfold}")
+    p = len(pan.xcols)
+    if tuple(coef.shape[1:]) != (3, p + 1):
+        raise ValueError(f"coef must be [nfold, 3, {p + 1}], got {tuple(coef.shape)}")
+    y0, y1, w0, w1 = _yw_columns(pan)
+    if not pan.data.is_cuda:
+        X = pan.colmajor().double()
+        c = coef.double()
+        mom = torch.zeros(N_MOMENTS, dtype=torch.float64)
+        lo, hi = clip, 1.0 - clip
+        for s in range(nseg):
+            r0, r1 = (int(v) for v in pan.seg_bounds[s])
+            Xs = X[:, r0:r1]
+            v = Xs[pan.cols["one"]] != 0
+            xs = Xs[pan.xcols][:, v]
+            y = Xs[y0][v] + (Xs[y1][v] if y1 >= 0 else 0.0)
+            w = Xs[w0][v] + (Xs[w1][v] if w1 >= 0 else 0.0)
+            k = s // segs_per_fold
+            g0 = c[k, 0, 0] + c[k, 0, 1:] @ xs
+            g1 = c[k, 1, 0] + c[k, 1, 1:] @ xs
+            m = c[k, 2, 0] + c[k, 2, 1:] @ xs
+            e = m.clamp(lo, hi)
+            psi = g1 - g0 + w * (y - g1) / e - (1.0 - w) * (y - g0) / (1.0 - e)
+            one = torch.ones_like(psi)
+            mom += torch.stack([psi.sum(), (psi * psi).sum(), one.sum(),
+                                ((m < lo) | (m > hi)).double().sum(),
+                                (w * (y - g1) ** 2).sum(), ((1.0 - w) * (y - g0) ** 2).sum(),
+                                ((w - m) ** 2).sum(), w.sum()])
+        return mom
+    dev = pan.device
+    xc = const(pan.xcols, torch.int32, dev)
+    segs = const(np.asarray(pan.seg_bounds, dtype=np.int64), torch.int64, dev)
+    if nbx is None:
+        # bf16: 2048 rows per block; enough blocks per segment to fill 256 CUs several times
+        nbx = 512 if pan.dtype == torch.bfloat16 else 256
+    part = torch.empty(nseg * nbx * N_MOMENTS, dtype=torch.float64, device=dev)
+    mom = torch.empty(N_MOMENTS, dtype=torch.float64, device=dev)
+    c = coef.double().contiguous()
+    cs, bs = pan.strides()
+    _native.call("ate_irm_score_moments", dtype_code(pan.data), pan.data.data_ptr(), cs, bs,
+                 xc.data_ptr(), p, segs.data_ptr(), nseg, segs_per_fold, c.data_ptr(), y0, y1,
+                 w0, w1, pan.cols["one"], float(clip), nbx, part.data_ptr(), mom.data_ptr(),
+                 torch.cuda.current_stream().cuda_stream)
+    return mom
+
+
+def irm_finalize(mom: torch.Tensor) -> torch.Tensor:
+    """[theta, SE] from the score moments: theta = S psi / n, SE^2 = the sample variance of
+    psi over n (clamped at 0). Device tensors in and out, no host sync (capturable)."""
+    n = mom[2]
+    theta = mom[0] / n
+    var = ((mom[1] - mom[0] * mom[0] / n) / (n - 1) / n).clamp(min=0)
+    return torch.stack([theta, torch.sqrt(var)])
+
+
+def check_cells(counts, folds: int):
+    """Every (fold, arm) cell of the 2K-segment layout needs a row: the per-arm outcome fit
+    of every other fold trains on it. ``counts``: (global) rows per segment."""
+    c = np.asarray(counts)
+    if len(c) != 2 * folds:
+        raise ValueError(f"DML-IRM needs {2 * folds} segments (fold k, arm a -> 2k + a), "
+                         f"the panel has {len(c)}")
+    for s in np.flatnonzero(c <= 0):
+        raise ValueError(f"empty (fold, arm) cell: fold {int(s) // 2}, arm W={int(s) % 2} "
+                         "has no rows")
+
+
+def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_counts=None):
+    """The cross-fit DML-IRM step as phases for utils.graphs.SegmentedStep (as
+    lasso.dml_phases):
+
+    A  per-(fold, arm) Gram stack (K01): tile kernel, then slab reduce   device (two phases)
+    C01 all-reduce of the Gram stack over row shards                     collective (world > 1)
+    B  CV-LASSO paths for K folds x {g0, g1, m} + inner CV and the
+       lambda selection, one path launch (K08/K09)                       device
+    B' fused held-out AIPW score moments (csrc/irm.hip)                  device
+    C06 all-reduce of the 8 score moments                                collective (world > 1)
+    C  theta / SE (fp64, on device)                                      device
+
+    Every rank solves every path (paths are not sharded over ranks). The result state holds
+    "res" [2], "mom" [8], "coef" [K, 3, p+1] and "cv"."""
+    from ..utils.graphs import Collective
+    dist = comm is not None and comm.world_size > 1
+    K = folds
+    if seg_counts is None:
+        seg_counts = global_seg_counts(pan, comm) if dist else np.asarray(pan.seg_nreal)
+    counts = np.asarray(seg_counts, dtype=np.float64)
+    check_cells(counts, K)
+    if pan.nseg != 2 * K:
+        raise ValueError(f"DML-IRM needs {2 * K} segments, this shard's panel has {pan.nseg}")
+    # segments of the 3K-Gram stack: 2s + a = (fold s, arm a); 2K + s = fold s, both arms
+    counts3 = np.concatenate([counts, counts[0::2] + counts[1::2]])
+    full_sets, full_y = [], []
+    for k in range(K):
+        others = [s for s in range(K) if s != k]
+        full_sets += [[2 * s for s in others], [2 * s + 1 for s in others],
+                      [2 * K + s for s in others]]
+        full_y += [0, 0, 1]                       # g0, g1: target Y; m: target W
+    ycols = [pan.cols["Y"], pan.cols["W"]]
+
+    def phase_gram(_):
+        return {"G": gram(pan, stage="tiles")}
+
+    def phase_gram_reduce(st):
+        return {"G": gram(pan, stage="reduce", out=st["G"])}
+
+    def phase_fit(st):
+        G = st["G"]
+        G3 = torch.cat([G, G[0::2] + G[1::2]])
+        cv = cv_enet_gaussian(G3, pan, pan.xcols, ycols, full_sets=full_sets,
+                              seg_counts=counts3, full_y=full_y)
+        coef = (cv.coef_min if lambda_rule == "min" else cv.coef_1se).reshape(K, 3, -1)
+        return {**st, "cv": cv, "coef": coef.double().contiguous()}
+
+    def phase_score(st):
+        return {**st, "mom": irm_score_moments(pan, st["coef"], clip, 2)}
+
+    def phase_final(st):
+        return {**st, "res": irm_finalize(st["mom"])}
+
+    cap = bool(getattr(comm, "capturable", False))
+
+    def reduce(name):
+        def f(st):
+            comm.all_reduce_(st[name])
+            return st
+        return Collective(f, capturable=cap)     # RCCL: captured inside the step's graph
+
+    def reduce_sym(name):
+        _tri_index(pan.P, pan.device)            # built here, never inside a capture
+
+        def f(st):
+            allreduce_sym_(comm, st[name])
+            return st
+        return Collective(f, capturable=cap)
+
+    phases = [phase_gram, phase_gram_reduce]
+    if dist:
+        phases.append(reduce_sym("G"))
+    phases += [phase_fit, phase_score]
+    if dist:
+        phases.append(reduce("mom"))
+    phases.append(phase_final)
+    return phases
+
+
+def irm_crossfit_panel(pan, folds: int, lambda_rule="min", clip=0.01, comm=None,
+                       seg_counts=None):
+    """DML-IRM on an arm-split fold panel (segment 2k + a = fold k, W = a; from host arrays
+    ``build_panel(X, W, Y, folds=2 * fold + W)``, at scale
+    ``data.device_dgp.synthetic_panel(arm_split=True)``). Returns (res[2], mom[8], cv).
+
+    comm: optional parallel.comm.Communicator -- each rank holds a row shard of every
+    segment; the Gram stack and the score moments are all-reduced. seg_counts: global rows
+    per segment (one all-reduce when omitted). A truncated CV fold path NaN-poisons the
+    picked coefficients (ops/enet), and through them res."""
+    st = None
+    for ph in irm_phases(pan, folds, lambda_rule, clip, comm, seg_counts):
+        st = ph(st)
+    return st["res"], st["mom"], st.get("cv")
+
+
+def _irm_body(pan, folds, lambda_rule, clip, dist=None, counts=None):
+    """The whole cross-fit as one device function (GraphCache captures it): [res, mom]."""
+    comm = dist.comm if dist is not None else None
+    res, mom, _ = irm_crossfit_panel(pan, folds, lambda_rule, clip, comm=comm,
+                                     seg_counts=None if counts is None else np.asarray(counts))
+    return torch.cat([res, mom])
+
+
+def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                  method="DML-IRM cross-fit (LASSO)", device=None, dtype="f64", dist=None,
+                  graph=True):
+    """K-fold cross-fitted AIPW (interactive model) with CV-LASSO nuisances: per-arm
+    outcome regressions and the linear-probability propensity, each with an inner CV over
+    the other K-1 folds (the fold stream of dml_plr_lasso). W must be exactly {0, 1}.
+    Matches reference.estimators.dml_irm_lasso.
+
+    graph: on a GPU (alone, or row-sharded over RCCL) the estimator runs as one captured
+    hipGraph (first call of a panel layout eager, captured on the second, replayed after).
+    diagnostics: n, n_clipped (propensities outside [clip, 1-clip]), n_treated, the held-out
+    RMSE of the three nuisances, hipgraph."""
+    dev = resolve_device(device)
+    Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
+    if not np.isin(Wn, (0.0, 1.0)).all():
+        raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
+    fid = _fold_ids(len(Yn), folds, seed, 0, dist)
+    seg = 2 * np.asarray(fid, dtype=np.int64) + Wn.astype(np.int64)
+    local = np.bincount(seg, minlength=2 * folds).astype(np.float64)
+    counts = local
+    if dist is not None and dist.world > 1:
+        t = torch.as_tensor(local).to(dev)
+        dist.sum_(t)
+        counts = t.cpu().numpy()
+    check_cells(counts, folds)
+    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev)
+    n = dist.n_total if dist is not None else len(Yn)
+    g = False
+    if graph and (dist is None or dist.capturable) and pan.data.is_cuda:
+        out, g = estimator_graphs.run("dml_irm", _irm_body, (pan,), folds, lambda_rule,
+                                      float(clip), dist, tuple(counts.tolist()))
+    else:
+        out = _irm_body(pan, folds, lambda_rule, clip, dist, counts)
+    v = out.detach().double().cpu().numpy()
+    mom = v[2:]
+    nt = mom[7]
+    diag = dict(n=n, n_clipped=int(round(mom[3])) if np.isfinite(mom[3]) else -1,
+                n_treated=int(round(nt)) if np.isfinite(nt) else -1,
+                rmse_g0=float(np.sqrt(mom[5] / (mom[2] - nt))),
+                rmse_g1=float(np.sqrt(mom[4] / nt)), rmse_m=float(np.sqrt(mom[6] / mom[2])),
+                hipgraph=g)
+    return AteResult.make(method, v[0], v[1], **diag)

@@ -79,12 +79,17 @@ def _rescale_vp(vp, p):
 
 def cv_enet_gaussian(G: torch.Tensor, panel, xcols, ycols, full_sets=None, penalty_factor=None,
                      alpha=1.0, nlambda=100, lambda_min_ratio=None, thresh=1e-7,
-                     maxit=100000, seg_counts=None) -> EnetCvResult:
+                     maxit=100000, seg_counts=None, full_y=None) -> EnetCvResult:
     """Cross-validated gaussian elastic net from the segment Gram stack ``G`` [nseg,P,P].
 
     full_sets: list of lists of segment ids (default: one set with all segments).
     seg_counts: rows per segment (default: the panel's; pass the GLOBAL counts when G
-    was all-reduced over row shards). Problems are ordered (full set f, y index)."""
+    was all-reduced over row shards). Problems are ordered (full set f, y index).
+    full_y: one index into ``ycols`` per full set: full set f is then solved for that
+    target only (one problem per full set, e.g. per-arm outcome and propensity nuisances
+    in one launch); default: every full set for every target. The target statistics of a
+    (training set, y) pair no problem names are computed but never read (a zero-variance
+    target there gets scale 1, csrc/enet.hip enet_prep_stats_kernel / _cv_cpu)."""
     nseg = G.shape[0]
     P = G.shape[1]
     p = len(xcols)
@@ -118,25 +123,29 @@ def cv_enet_gaussian(G: torch.Tensor, panel, xcols, ycols, full_sets=None, penal
         lambda_min_ratio = 1e-4 if min(n_full) > p else 1e-2
     vp = _rescale_vp(penalty_factor, p)
     L = nlambda
+    if full_y is None:
+        ys_of = [list(range(ny))] * len(full_sets)
+    else:
+        if len(full_y) != len(full_sets) or any(not 0 <= int(y) < ny for y in full_y):
+            raise ValueError("full_y needs one index into ycols per full set")
+        ys_of = [[int(y)] for y in full_y]
     # problem tables
-    full_probs = [(full_t[f], y, -1, nlambda) for f in range(len(full_sets)) for y in range(ny)]
-    full_keys = [(f, y) for f in range(len(full_sets)) for y in range(ny)]
-    fold_probs, fold_ycol, fold_holds, fold_of_full = [], [], [], []
-    for f in range(len(full_sets)):
-        for k in range(K):
-            for y in range(ny):
-                src = f * ny + y
-                fold_probs.append((fold_t[f * K + k], y, src, 0))
-                fold_ycol.append(ycols[y])
-                fold_holds.append(fold_hold[f * K + k])
-    # fold_probs index for (full problem fp, k): order above is f, k, y
+    full_keys = [(f, y) for f in range(len(full_sets)) for y in ys_of[f]]
+    full_probs = [(full_t[f], y, -1, nlambda) for f, y in full_keys]
+    src_of = {key: i for i, key in enumerate(full_keys)}
+    fold_probs, fold_ycol, fold_holds = [], [], []
+    # fold_probs index for (full problem fp, k): order is f, k, y
     fold_index = np.zeros((len(full_probs), K), dtype=np.int32)
     nfold = np.zeros((len(full_probs), K))
     for f in range(len(full_sets)):
         for k in range(K):
-            for y in range(ny):
-                fold_index[f * ny + y, k] = (f * K + k) * ny + y
-                nfold[f * ny + y, k] = nreal[fold_hold[f * K + k]]
+            for y in ys_of[f]:
+                src = src_of[(f, y)]
+                fold_index[src, k] = len(fold_probs)
+                nfold[src, k] = nreal[fold_hold[f * K + k]]
+                fold_probs.append((fold_t[f * K + k], y, src, 0))
+                fold_ycol.append(ycols[y])
+                fold_holds.append(fold_hold[f * K + k])
     # group fold problems by training set (the path kernel places consecutive problems
     # on the same XCD, so problems sharing a Gram share an L2)
     perm = np.argsort([fp[0] for fp in fold_probs], kind="stable")

@@ -347,6 +347,47 @@ def dml_plr_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min",
     return dml_from_residuals(yr, wr, method)
 
 
+def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                  method="DML-IRM cross-fit (LASSO)", fold_ids=None):
+    """Cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1) with
+    CV-LASSO nuisances, row by row in float64: for held-out fold k, g0 and g1 are gaussian
+    LASSO fits of Y on the training rows of each arm and m is the linear-probability LASSO of
+    W on all training rows, each with lambda chosen by (K-1)-fold CV over the training folds
+    (as dml_plr_lasso). Score (textbook signs): psi = g1 - g0 + W (Y - g1) / m
+    - (1 - W)(Y - g0) / (1 - m) with m clipped to [clip, 1 - clip]; theta = mean(psi),
+    SE = sd(psi) / sqrt(n)."""
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    if not np.isin(W, (0.0, 1.0)).all():
+        raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
+    fid = rng.fold_ids(len(Y), folds, seed, stream=0) if fold_ids is None else \
+        np.asarray(fold_ids, dtype=np.int64)
+    for k in range(folds):
+        for a in (0, 1):
+            if not np.any((fid == k) & (W == a)):
+                raise ValueError(f"empty (fold, arm) cell: fold {k}, arm W={a} has no rows")
+    s = "lambda.min" if lambda_rule == "min" else "lambda.1se"
+    g0 = np.empty_like(Y)
+    g1 = np.empty_like(Y)
+    m = np.empty_like(Y)
+    for k in range(folds):
+        te = fid == k
+        inner = np.where(fid > k, fid - 1, fid)
+        for rows, target, out in (((~te) & (W == 0), Y, g0), ((~te) & (W == 1), Y, g1),
+                                  (~te, W, m)):
+            cv = gn.cv_glmnet(X[rows], target[rows], foldid=inner[rows])
+            out[te] = cv.predict(X[te], s=s)
+    e = np.clip(m, clip, 1 - clip)
+    psi = g1 - g0 + W * (Y - g1) / e - (1 - W) * (Y - g0) / (1 - e)
+    n = len(Y)
+    nt = W.sum()
+    return AteResult.make(method, psi.mean(), psi.std(ddof=1) / np.sqrt(n), n=n,
+                          n_clipped=int(((m < clip) | (m > 1 - clip)).sum()),
+                          n_treated=int(nt),
+                          rmse_g0=float(np.sqrt(((1 - W) * (Y - g0) ** 2).sum() / (n - nt))),
+                          rmse_g1=float(np.sqrt((W * (Y - g1) ** 2).sum() / nt)),
+                          rmse_m=float(np.sqrt(((W - m) ** 2).mean())))
+
+
 def dml_plr_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="min",
                            aggregate="median", method="DML cross-fit (LASSO, repeated)"):
     """Repeated cross-fitting (Chernozhukov et al. 2018 §3.4, median method): S = repeats

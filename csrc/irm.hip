@@ -1,0 +1,299 @@
+// Fused held-out score pass of the cross-fitted interactive model (DML-IRM, AIPW score)
+// with linear nuisances.
+//
+// For every row i of segment s, with the coefficient triple of block k = s / segs_per_fold
+// (segs_per_fold = 2: the arm-split layout, segment 2k + a = rows of fold k with W = a;
+// 1: a plain K-fold panel):
+//   g0_i = c0[0] + x_i . c0[1:],  g1_i = c1[0] + x_i . c1[1:],  m_i = cm[0] + x_i . cm[1:]
+//   e_i  = min(max(m_i, clip), 1 - clip)
+//   psi_i = g1_i - g0_i + w_i (y_i - g1_i) / e_i - (1 - w_i) (y_i - g0_i) / (1 - e_i)
+// and the 8 moments
+//   {S psi, S psi^2, n, n_clipped, S w (y - g1)^2, S (1 - w)(y - g0)^2, S (w - m)^2, n_treated}
+// are accumulated in fp64: no per-row value is written to HBM. w is read from the panel
+// on every row, never inferred from the segment. Only the columns in the union of the three
+// LASSO supports are read, once each; the coefficient triple is staged in LDS. y / w are
+// rebuilt from their hi + lo bf16 columns on bf16 panels. Structure as csrc/dml.hip.
+#include "common.hpp"
+
+using namespace ate;
+
+namespace {
+
+constexpr int NM = 8;   // moments
+
+template <typename T>
+__device__ __forceinline__ double ld_col(const T* X, int64_t ld, int c, int64_t i) {
+  return (double)X[(int64_t)c * ld + i];
+}
+
+struct Seg { int64_t r0, r1; };
+
+// Ordered compaction (ascending j: the dot products keep the summation order of the dense
+// loop, bit for bit) of the feature columns with a nonzero coefficient in any of the three
+// nuisances. c0/c1/cm/xc: dense staged arrays, compacted in place (c*[1+q], xc[q] for
+// q < return value). The whole block must call it.
+template <typename C>
+__device__ int compact_support3(C* c0, C* c1, C* cm, int* xc, int p, int* wcnt /* [>= 16] */) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  int base = 0;
+  for (int j0 = 0; j0 < p; j0 += blockDim.x) {
+    const int j = j0 + threadIdx.x;
+    const C v0 = j < p ? c0[1 + j] : C(0), v1 = j < p ? c1[1 + j] : C(0),
+            vm = j < p ? cm[1 + j] : C(0);
+    const bool keep = v0 != C(0) || v1 != C(0) || vm != C(0);
+    const int c = j < p ? xc[j] : 0;
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) wcnt[wid] = __popcll(m);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wid; ++w) off += wcnt[w];
+    int tot = base;
+    for (int w = 0; w < nw; ++w) tot += wcnt[w];
+    const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();                                      // all reads of the dense slots done
+    ATE_DASSERT(pos <= j);                                // compaction only moves entries down
+    if (keep) { c0[1 + pos] = v0; c1[1 + pos] = v1; cm[1 + pos] = vm; xc[pos] = c; }
+    __syncthreads();
+    base = tot;
+  }
+  return base;
+}
+
+// one valid row's contribution (everything after the three dot products, fp64)
+__device__ __forceinline__ void irm_accumulate(double (&v)[NM], double y, double w, double g0,
+                                               double g1, double m, double clip) {
+  const double lo = clip, hi = 1.0 - clip;
+  const double e = m < lo ? lo : (m > hi ? hi : m);
+  const double r1 = y - g1, r0 = y - g0, rm = w - m;
+  const double psi = g1 - g0 + w * r1 / e - (1.0 - w) * r0 / (1.0 - e);
+  v[0] += psi;
+  v[1] += psi * psi;
+  v[2] += 1.0;
+  v[3] += (m < lo || m > hi) ? 1.0 : 0.0;
+  v[4] += w * (r1 * r1);
+  v[5] += (1.0 - w) * (r0 * r0);
+  v[6] += rm * rm;
+  v[7] += w;
+}
+
+__device__ __forceinline__ void write_partial(double (&v)[NM], double* red, double* partial) {
+  block_sum<NM>(v, red);
+  if (threadIdx.x == 0) {
+    double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * NM;
+#pragma unroll
+    for (int q = 0; q < NM; ++q) out[q] = v[q];
+  }
+}
+
+// fp32 / fp64 column-major panels: fp64 dot products, RPT rows per thread 256 apart
+template <typename T, int RPT>
+__global__ __launch_bounds__(256) void irm_score_kernel(
+    const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p, int P,
+    const Seg* __restrict__ segs, int nseg, int spf,
+    const double* __restrict__ coef /*[nfold][3][p+1]*/, int y0, int y1, int w0, int w1,
+    int vcol, double clip, double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  double* c0 = sh;                      // [p+1]
+  double* c1 = sh + (p + 1);            // [p+1]
+  double* cm = sh + 2 * (p + 1);        // [p+1]
+  int* xc = (int*)(sh + 3 * (p + 1));   // [p]
+  __shared__ double red[16 * NM];       // static LDS: 1024 + 64 bytes (a multiple of 16)
+  __shared__ int wcnt[16];
+  const int s = blockIdx.y, k = s / spf;
+  ATE_DASSERT(s < nseg && spf >= 1 && y0 >= 0 && w0 >= 0 && vcol >= 0);
+  ATE_DASSERT(P == 0 || (y0 < P && w0 < P && vcol < P && y1 < P && w1 < P));
+  for (int j = threadIdx.x; j < p; j += blockDim.x) {
+    xc[j] = xcols[j];
+    ATE_DASSERT(xc[j] >= 0 && (P == 0 || xc[j] < P));
+  }
+  for (int j = threadIdx.x; j <= p; j += blockDim.x) {
+    c0[j] = coef[((int64_t)k * 3 + 0) * (p + 1) + j];
+    c1[j] = coef[((int64_t)k * 3 + 1) * (p + 1) + j];
+    cm[j] = coef[((int64_t)k * 3 + 2) * (p + 1) + j];
+  }
+  __syncthreads();
+  p = compact_support3(c0, c1, cm, xc, p, wcnt);
+  const Seg sg = segs[s];
+  ATE_DASSERT(sg.r0 >= 0 && sg.r0 <= sg.r1 && sg.r1 <= ld);
+  double v[NM] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t base = sg.r0 + (int64_t)blockIdx.x * 256 * RPT; base < sg.r1;
+       base += (int64_t)gridDim.x * 256 * RPT) {
+    double a0[RPT], a1[RPT], am[RPT];
+    int64_t ii[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      ii[r] = base + r * 256 + threadIdx.x;
+      a0[r] = c0[0];
+      a1[r] = c1[0];
+      am[r] = cm[0];
+    }
+    for (int j = 0; j < p; ++j) {
+      const double b0 = c0[1 + j], b1 = c1[1 + j], bm = cm[1 + j];
+      const int c = xc[j];
+#pragma unroll
+      for (int r = 0; r < RPT; ++r) {
+        const double x = ii[r] < sg.r1 ? ld_col(X, ld, c, ii[r]) : 0.0;
+        a0[r] += b0 * x;
+        a1[r] += b1 * x;
+        am[r] += bm * x;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      if (ii[r] >= sg.r1) continue;
+      if (ld_col(X, ld, vcol, ii[r]) == 0.0) continue;          // padding row
+      const double y = ld_col(X, ld, y0, ii[r]) + (y1 >= 0 ? ld_col(X, ld, y1, ii[r]) : 0.0);
+      const double w = ld_col(X, ld, w0, ii[r]) + (w1 >= 0 ? ld_col(X, ld, w1, ii[r]) : 0.0);
+      ATE_DASSERT(spf != 2 || w == (double)(s & 1));
+      irm_accumulate(v, y, w, a0[r], a1[r], am[r], clip);
+    }
+  }
+  write_partial(v, red, partial);
+}
+
+// bf16 panels: each thread owns 8 CONSECUTIVE rows, so every column read is one 16-byte
+// load through (cs, bs) (column-major and 64-row blocked panels); dot products in fp32
+// (bf16 values are exact in fp32; coefficients rounded to fp32), the score in fp64.
+__global__ __launch_bounds__(256) void irm_score_bf16_kernel(
+    const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
+    int P, int64_t ld, const Seg* __restrict__ segs, int nseg, int spf,
+    const double* __restrict__ coef, int y0, int y1, int w0, int w1, int vcol, double clip,
+    double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) float shf[];
+  float* c0 = shf;                       // [p+1]
+  float* c1 = shf + (p + 1);             // [p+1]
+  float* cm = shf + 2 * (p + 1);         // [p+1]
+  int* xc = (int*)(shf + 3 * (p + 1));   // [p]
+  __shared__ double red[16 * NM];
+  __shared__ int wcnt[16];
+  const int s = blockIdx.y, k = s / spf;
+  ATE_DASSERT(s < nseg && spf >= 1 && y0 >= 0 && w0 >= 0 && vcol >= 0);
+  ATE_DASSERT(P == 0 || (y0 < P && w0 < P && vcol < P && y1 < P && w1 < P));
+  for (int j = threadIdx.x; j < p; j += blockDim.x) {
+    xc[j] = xcols[j];
+    ATE_DASSERT(xc[j] >= 0 && (P == 0 || xc[j] < P));
+  }
+  for (int j = threadIdx.x; j <= p; j += blockDim.x) {
+    c0[j] = (float)coef[((int64_t)k * 3 + 0) * (p + 1) + j];
+    c1[j] = (float)coef[((int64_t)k * 3 + 1) * (p + 1) + j];
+    cm[j] = (float)coef[((int64_t)k * 3 + 2) * (p + 1) + j];
+  }
+  __syncthreads();
+  p = compact_support3(c0, c1, cm, xc, p, wcnt);
+  const Seg sg = segs[s];
+  ATE_DASSERT(sg.r0 >= 0 && sg.r0 <= sg.r1 && (ld == 0 || sg.r1 <= ld) && (sg.r0 & 7) == 0 &&
+              (sg.r1 & 7) == 0);
+  auto ld8 = [&](int c, int64_t i, float (&o)[8]) {
+    ATE_DASSERT((i & 7) == 0 && c >= 0 && (P == 0 || c < P) && (ld == 0 || i + 8 <= ld));
+    // (c, i) at c*cs + (i/64)*bs + i%64; the 8 rows never straddle a block (i % 8 == 0)
+    const uint4 u = *reinterpret_cast<const uint4*>(X + (int64_t)c * cs + (i >> 6) * bs + (i & 63));
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      o[2 * q] = __uint_as_float(w[q] << 16);
+      o[2 * q + 1] = __uint_as_float(w[q] & 0xFFFF0000u);
+    }
+  };
+  double v[NM] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t i = sg.r0 + ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < sg.r1;
+       i += (int64_t)gridDim.x * 256 * 8) {
+    float a0[8], a1[8], am[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { a0[r] = c0[0]; a1[r] = c1[0]; am[r] = cm[0]; }
+#pragma unroll 4
+    for (int j = 0; j < p; ++j) {
+      float x[8];
+      ld8(xc[j], i, x);
+      const float b0 = c0[1 + j], b1 = c1[1 + j], bm = cm[1 + j];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) { a0[r] += b0 * x[r]; a1[r] += b1 * x[r]; am[r] += bm * x[r]; }
+    }
+    float vv[8], ya[8], yb[8], wa[8], wb[8];
+    ld8(vcol, i, vv);
+    ld8(y0, i, ya);
+    ld8(w0, i, wa);
+    if (y1 >= 0) ld8(y1, i, yb); else { for (int r = 0; r < 8; ++r) yb[r] = 0.f; }
+    if (w1 >= 0) ld8(w1, i, wb); else { for (int r = 0; r < 8; ++r) wb[r] = 0.f; }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      if (vv[r] == 0.f) continue;                                 // padding row
+      const double y = (double)ya[r] + (double)yb[r];
+      const double w = (double)wa[r] + (double)wb[r];
+      ATE_DASSERT(spf != 2 || w == (double)(s & 1));
+      irm_accumulate(v, y, w, (double)a0[r], (double)a1[r], (double)am[r], clip);
+    }
+  }
+  write_partial(v, red, partial);
+}
+
+// one block of 256 threads: thread i sums partials i, i+256, ... (fixed order), then a
+// fixed-shape block reduction -> deterministic for a given launch geometry (the 8-moment
+// sibling of csrc/dml.hip sum7_kernel)
+__global__ __launch_bounds__(256) void irm_sum_kernel(const double* __restrict__ partial, int nb,
+                                                      double* __restrict__ out) {
+  __shared__ double red[16 * NM];
+  double v[NM] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int b = threadIdx.x; b < nb; b += 256)
+#pragma unroll
+    for (int q = 0; q < NM; ++q) v[q] += partial[(int64_t)b * NM + q];
+  block_sum<NM>(v, red);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int q = 0; q < NM; ++q) out[q] = v[q];
+}
+
+template <typename T>
+int irm_score_t(const void* X, int64_t ld, const void* xcols, int p, int P, const void* segs,
+                int nseg, int spf, const void* coef, int y0, int y1, int w0, int w1, int vcol,
+                double clip, int nbx, void* partial, size_t sh, hipStream_t s) {
+  ATE_LAUNCH((irm_score_kernel<T, 4>), dim3(nbx, nseg), dim3(256), sh, s, (const T*)X, ld,
+             (const int*)xcols, p, P, (const Seg*)segs, nseg, spf, (const double*)coef, y0, y1,
+             w0, w1, vcol, clip, (double*)partial);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+// dtype 1 f32, 2 f64, 3 bf16. (cs, bs): element (c, i) at c*cs + (i/64)*bs + i%64 (fp32 /
+// fp64 panels: column-major only, bs = 64). segs [nseg][2] int64 padded row ranges; coef
+// [ceil(nseg / segs_per_fold)][3][p+1] fp64, rows (g0, g1, m), intercept first.
+// partial: [nseg*nbx][8]; moments: [8].
+ATE_API int ate_irm_score_moments(int dtype, const void* X, int64_t cs, int64_t bs,
+                                  const void* xcols, int p, const void* segs, int nseg,
+                                  int segs_per_fold, const void* coef, int y0, int y1, int w0,
+                                  int w1, int vcol, double clip, int nbx, void* partial,
+                                  void* moments, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype < 1 || dtype > 3 || (dtype != 3 && bs != 64)) return -1;
+  if (p < 0 || nseg < 1 || nseg > 65535 || segs_per_fold < 1 || nbx < 1 || cs < 64 || bs < 64)
+    return -1;
+  if (y0 < 0 || w0 < 0 || vcol < 0) return -1;
+  // what the strides say about the panel's extent, for the debug build's bounds checks
+  // (0 = unknown): column-major (bs = 64) has ld = cs rows; 64-row blocked has P = bs / 64
+  const int64_t ld = bs == 64 ? cs : 0;
+  const int P = bs == 64 ? 0 : (int)(bs / 64);
+  if (!(clip >= 0.0 && clip < 0.5)) return -1;
+  const size_t esz = dtype == 3 ? sizeof(float) : sizeof(double);
+  const size_t sh = (size_t)3 * (p + 1) * esz + (size_t)p * sizeof(int);
+  if (sh > 64 * 1024 - 2048) return -1;     // dynamic + static LDS within the 64 KB default
+  int rc = -1;
+  if (dtype == 1)
+    rc = irm_score_t<float>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1, w0, w1,
+                            vcol, clip, nbx, partial, sh, s);
+  else if (dtype == 2)
+    rc = irm_score_t<double>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1, w0, w1,
+                             vcol, clip, nbx, partial, sh, s);
+  else {
+    ATE_LAUNCH(irm_score_bf16_kernel, dim3(nbx, nseg), dim3(256), sh, s, (const bf16_t*)X, cs, bs,
+               (const int*)xcols, p, P, ld, (const Seg*)segs, nseg, segs_per_fold,
+               (const double*)coef, y0, y1, w0, w1, vcol, clip, (double*)partial);
+    ATE_CHECK_LAUNCH();
+    rc = 0;
+  }
+  if (rc != 0) return rc;
+  ATE_LAUNCH(irm_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
+             (double*)moments);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""DML-IRM beside DML-PLR on one GPU: ms per captured call of ``irm_crossfit_panel`` and
+``dml_crossfit_panel`` on the same rows (tutorial DGP, bf16 blocked panels), alternated in
+one process and timed with device events. Recorded, not gated: profiles/irm/README.md.
+
+  python tools/irm_timing.py --n 1e7 --p 500 --calls 20
+
+``--score-only``: a few eager launches of the fused score pass alone after one fit, for a
+separate ``rocprofv3 --kernel-trace --stats -- python tools/irm_timing.py --score-only``
+run; the JSON line carries the bytes the pass reads, rows x (union support + 5 columns) x 2
+summed over the folds, to turn the kernel's time into bytes/s."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=float, default=1e7)
+    ap.add_argument("--p", type=int, default=500)
+    ap.add_argument("--folds", type=int, default=5)
+    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--blocked", type=int, default=1)
+    ap.add_argument("--dgp", default="tutorial")
+    ap.add_argument("--seed", type=int, default=1991)
+    ap.add_argument("--clip", type=float, default=0.01)
+    ap.add_argument("--calls", type=int, default=20, help="timed calls of each estimator")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--score-only", action="store_true")
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
+    from ate_replication_causalml_amd.estimators.irm import irm_phases, irm_score_moments
+    from ate_replication_causalml_amd.estimators.lasso import dml_phases
+    from ate_replication_causalml_amd.ops.gram import plan_slot
+    from ate_replication_causalml_amd.utils.graphs import SegmentedStep
+    dev = torch.device("cuda:0")
+    n, K = int(a.n), a.folds
+    blocked = bool(a.blocked) and a.dtype == "bf16"
+    kw = dict(p=a.p, folds=K, seed=a.seed, dtype=a.dtype, device=dev, blocked=blocked, dgp=a.dgp)
+    split = synthetic_panel(n, arm_split=True, **kw)
+    torch.cuda.synchronize()
+
+    def support_bytes(coef):
+        # rows x (union support + 5 columns: one, Y hi / lo, W hi / lo) x 2 bytes, per fold
+        nnz = (coef[:, :, 1:] != 0).any(1).sum(1).cpu().numpy()
+        rows = np.asarray(split.seg_nreal).reshape(K, 2).sum(1)
+        return nnz.tolist(), int((rows * (nnz + 5) * 2).sum())
+
+    if a.score_only:
+        st = None
+        for ph in irm_phases(split, K, "min", a.clip):
+            st = ph(st)
+        torch.cuda.synchronize()
+        for _ in range(5):
+            mom = irm_score_moments(split, st["coef"], a.clip, 2)
+        torch.cuda.synchronize()
+        nnz, nbytes = support_bytes(st["coef"])
+        print(json.dumps({"mode": "score-only", "n": n, "p": a.p, "launches": 6,
+                          "union_support": nnz, "score_bytes": nbytes,
+                          "res": st["res"].cpu().tolist(), "mom": mom.cpu().tolist()}))
+        return
+    plain = synthetic_panel(n, selection=split.selection, **kw)
+    with plan_slot(0):
+        plr = SegmentedStep(dml_phases(plain, K, "min"), graph=True, warmup=1)
+    with plan_slot(1):
+        irm = SegmentedStep(irm_phases(split, K, "min", a.clip), graph=True, warmup=1)
+    for _ in range(a.warmup):
+        plr()
+        irm()
+    torch.cuda.synchronize()
+    ms = {"plr": [], "irm": []}
+    for _ in range(a.calls):                      # alternate: both see the same clocks
+        for name, step in (("plr", plr), ("irm", irm)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            st = step()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1))
+    nnz, nbytes = support_bytes(irm()["coef"])
+    torch.cuda.synchronize()
+    out = {"n": n, "p": a.p, "folds": K, "dtype": a.dtype, "blocked": blocked, "dgp": a.dgp,
+           "calls": a.calls, "graphed": [plr.graphed, irm.graphed]}
+    for name in ms:
+        v = ms[name]
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "mean_ms": statistics.fmean(v)}
+    out["ratio_irm_over_plr"] = out["irm"]["median_ms"] / out["plr"]["median_ms"]
+    out["plr_res"] = plr()["res"].cpu().tolist()
+    out["irm_res"] = irm()["res"].cpu().tolist()
+    out["irm_mom"] = irm()["mom"].cpu().tolist()
+    out["union_support"], out["score_bytes"] = nnz, nbytes
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
