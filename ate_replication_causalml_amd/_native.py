@@ -99,6 +99,9 @@ _SIGS = {
     "ate_dml_resid_moments": "ipllpipipiiiiiippp",
     "ate_dml_resid_exact": "pllpipipiiiiiiippp",
     "ate_irm_score_moments": "ipllpipiipiiiiidippp",
+    "ate_irm_scores": "ipllpipiipiiiiidipp",
+    "ate_group_boot": "pppliiuippp",
+    "ate_group_boot_scratch": "iii",
     "ate_lognet_path": "iplpiipipipdddippippppppppp",
     "ate_lognet_cvloss": "iplpiippipppipp",
     "ate_dgp_fill": "iplllllp" + "uiipppp",
@@ -141,7 +144,7 @@ _SIGS = {
 _RESTYPE = {"ate_forest_scratch_bytes": ctypes.c_int64,
             "ate_forest_exact_scratch_bytes": ctypes.c_int64, "ate_gbdt_slab_entries": ctypes.c_int64,
             "ate_gbdt_slab2_entries": ctypes.c_int64,
-            "ate_scan_parts": ctypes.c_int64}
+            "ate_scan_parts": ctypes.c_int64, "ate_group_boot_scratch": ctypes.c_int64}
 _CT = {"p": c_void_p, "i": c_int, "l": c_int64, "u": c_uint64, "d": c_double}
 
 

@@ -17,7 +17,8 @@ ate_lasso; prop_score_lasso -> propensity_lasso; doubly_robust -> ate_aipw_rf;
 doubly_robust_glm -> ate_aipw_glm; belloni -> ate_belloni; double_ml ->
 ate_double_ml; residual_balance_ATE -> ate_residual_balance; grf::causal_forest +
 estimate_average_effect -> ate_causal_forest; K-fold DML-PLR -> ate_dml; K-fold DML-IRM
-(cross-fitted AIPW, LASSO nuisances) -> ate_dml_irm.
+(cross-fitted AIPW, LASSO nuisances) -> ate_dml_irm; its group effects with a joint
+multiplier-bootstrap band (DoubleML gate / bootstrap / confint(joint=True)) -> ate_dml_irm_gate.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import AteResult, format_table, results_frame
+from .result import AteResult, GateResult, format_table, results_frame
 from .utils import guards
 from .utils.tracing import trace
 
@@ -248,6 +249,26 @@ def ate_dml_irm(Y, W, X, folds=5, lambda_rule="min", clip=0.01,
                                 clip=clip, method=method, device=run.device(), dtype=run.dtype)
 
 
+def ate_dml_irm_gate(Y, W, X, groups, folds=5, lambda_rule="min", clip=0.01, n_boot=999,
+                     level=0.95, method="DML-IRM group ATEs (LASSO)", run=None) -> GateResult:
+    """Group average treatment effects of ate_dml_irm -- the mean AIPW score within each
+    group of ``groups`` (an (n,) vector of labels; at most 64 groups) -- with pointwise and
+    simultaneous ``level`` confidence bounds, the latter from ``n_boot`` Rademacher
+    multiplier-bootstrap draws of the maximal t-statistic (estimators/gate.py)."""
+    run = _run(run)
+    with trace("ate_dml_irm_gate", folds=folds, n_boot=n_boot):
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_irm_gate(Y, W, X, groups, folds=folds, seed=run.seed,
+                                  lambda_rule=lambda_rule, clip=clip, n_boot=n_boot, level=level,
+                                  method=method)
+        from .estimators import gate as DG
+        return DG.dml_irm_gate_lasso(Y, W, X, groups, folds=folds, seed=run.seed,
+                                     lambda_rule=lambda_rule, clip=clip, n_boot=n_boot,
+                                     level=level, method=method, device=run.device(),
+                                     dtype=run.dtype)
+
+
 def ate_residual_balance(Y, W, X, balance: BalanceConfig | None = None,
                          method="residual_balancing", run=None) -> AteResult:
     """E14 residual_balance_ATE (ate_functions.R:393-405) -> balanceHD::residualBalance.ate."""
@@ -421,7 +442,7 @@ def replicate(data=None, config: ReplicateConfig | None = None, log_path=None, p
 __all__ = [
     "ate_naive", "ate_ols", "propensity_logistic", "propensity_lasso", "ate_ipw", "ate_ipw_wls",
     "ate_lasso_single", "ate_lasso", "ate_aipw_rf", "ate_aipw_glm", "ate_belloni",
-    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_residual_balance", "ate_causal_forest", "replicate",
+    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_residual_balance", "ate_causal_forest", "replicate",
     "ate_aipw_crossfit", "ate_causal_forest_bootstrap",
-    "Replication", "AteResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
+    "Replication", "AteResult", "GateResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
 ]

@@ -48,6 +48,23 @@ def _dml(a):
             raise SystemExit("--model irm has no repeated cross-fitting")
         pan = synthetic_panel(a.n, p=a.p, folds=a.folds, seed=a.seed, dtype=a.dtype, device=dev,
                               arm_split=True)
+        if a.gate_col is not None:
+            # group effects over quantile bins of covariate x{gate_col}, with a joint band
+            from .estimators.gate import irm_gate_panel, quantile_groups
+            from .result import AteResult, GateResult
+            gid, edges = quantile_groups(pan, a.gate_col, a.gate_bins)
+            fin, _, _ = irm_gate_panel(pan, gid, a.folds, a.lambda_rule, a.clip, n_boot=a.boot,
+                                       seed=a.seed)
+            v = fin.double().cpu().numpy()
+            G = a.gate_bins
+            r = GateResult.make("DML-IRM group ATEs (LASSO)", list(range(G)), v[2 * G:3 * G],
+                                v[:G], v[G:2 * G], v[3 * G], a.boot, 0.95,
+                                AteResult.make("DML-IRM cross-fit (LASSO)", v[3 * G + 1],
+                                               v[3 * G + 2], n=a.n))
+            out = {"groups": r.rows(), "crit": r.crit, "n_boot": r.n_boot, "level": r.level,
+                   "edges": edges.cpu().tolist(), "ate": r.overall.ate, "se": r.overall.se}
+            print(json.dumps(out))
+            return 0
         res, mom, cv = irm_crossfit_panel(pan, a.folds, a.lambda_rule, a.clip)
         r = read_result(res, "DML-IRM cross-fit (LASSO)", n=a.n)
         out = {"ate": r.ate, "se": r.se, "lower_ci": r.lower_ci, "upper_ci": r.upper_ci,
@@ -113,6 +130,11 @@ def main(argv=None):
                    help="plr: partially linear model; irm: interactive model (cross-fitted AIPW)")
     d.add_argument("--clip", type=float, default=0.01,
                    help="irm: the propensity is clipped to [clip, 1 - clip]")
+    d.add_argument("--gate-col", type=int, default=None,
+                   help="irm: group ATEs over quantile bins of covariate x{J}, with a joint band")
+    d.add_argument("--gate-bins", type=int, default=4, help="irm --gate-col: quantile groups")
+    d.add_argument("--boot", type=int, default=999,
+                   help="irm --gate-col: multiplier-bootstrap draws of the joint band")
     d.set_defaults(fn=_dml)
     b = sub.add_parser("build")
     b.set_defaults(fn=_build)

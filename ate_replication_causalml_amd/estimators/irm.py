@@ -100,6 +100,57 @@ def irm_score_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold
     return mom
 
 
+def irm_scores(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
+               nbx: int | None = None) -> torch.Tensor:
+    """The per-row AIPW scores psi [ld] (fp64, panel row order, 0 on padding rows): the pass
+    of :func:`irm_score_moments` -- same arguments, same dot products, same psi -- writing
+    every row's score instead of summing moments (csrc/irm.hip ``ate_irm_scores``; CPU: the
+    float64 torch twin). Input of the grouped multiplier bootstrap (estimators/gate.py)."""
+    nseg = pan.nseg
+    nfold = coef.shape[0]
+    if segs_per_fold < 1 or nfold * segs_per_fold < nseg:
+        raise ValueError(f"{nseg} segments at {segs_per_fold} per fold need "
+                         f"{-(-nseg // max(segs_per_fold, 1))} coefficient blocks, got {nfold}")
+    p = len(pan.xcols)
+    if tuple(coef.shape[1:]) != (3, p + 1):
+        raise ValueError(f"coef must be [nfold, 3, {p + 1}], got {tuple(coef.shape)}")
+    y0, y1, w0, w1 = _yw_columns(pan)
+    if not pan.data.is_cuda:
+        X = pan.colmajor().double()
+        c = coef.double()
+        psi = torch.zeros(pan.ld, dtype=torch.float64)
+        for s in range(nseg):
+            r0, r1 = (int(v) for v in pan.seg_bounds[s])
+            Xs = X[:, r0:r1]
+            v = Xs[pan.cols["one"]] != 0
+            xs = Xs[pan.xcols][:, v]
+            y = Xs[y0][v] + (Xs[y1][v] if y1 >= 0 else 0.0)
+            w = Xs[w0][v] + (Xs[w1][v] if w1 >= 0 else 0.0)
+            k = s // segs_per_fold
+            g0 = c[k, 0, 0] + c[k, 0, 1:] @ xs
+            g1 = c[k, 1, 0] + c[k, 1, 1:] @ xs
+            e = (c[k, 2, 0] + c[k, 2, 1:] @ xs).clamp(clip, 1.0 - clip)
+            seg = psi[r0:r1]
+            seg[v] = g1 - g0 + w * (y - g1) / e - (1.0 - w) * (y - g0) / (1.0 - e)
+        return psi
+    bounds = np.asarray(pan.seg_bounds, dtype=np.int64)
+    if bounds[0, 0] != 0 or bounds[-1, 1] != pan.ld or np.any(bounds[1:, 0] != bounds[:-1, 1]):
+        raise ValueError("the panel's segments must tile [0, ld): every row gets a score")
+    dev = pan.device
+    xc = const(pan.xcols, torch.int32, dev)
+    segs = const(bounds, torch.int64, dev)
+    if nbx is None:
+        nbx = 512 if pan.dtype == torch.bfloat16 else 256
+    psi = torch.empty(pan.ld, dtype=torch.float64, device=dev)
+    c = coef.double().contiguous()
+    cs, bs = pan.strides()
+    _native.call("ate_irm_scores", dtype_code(pan.data), pan.data.data_ptr(), cs, bs,
+                 xc.data_ptr(), p, segs.data_ptr(), nseg, segs_per_fold, c.data_ptr(), y0, y1,
+                 w0, w1, pan.cols["one"], float(clip), nbx, psi.data_ptr(),
+                 torch.cuda.current_stream().cuda_stream)
+    return psi
+
+
 def irm_finalize(mom: torch.Tensor) -> torch.Tensor:
     """[theta, SE] from the score moments: theta = S psi / n, SE^2 = the sample variance of
     psi over n (clamped at 0). Device tensors in and out, no host sync (capturable)."""
@@ -135,6 +186,25 @@ def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_cou
 
     Every rank solves every path (paths are not sharded over ranks). The result state holds
     "res" [2], "mom" [8], "coef" [K, 3, p+1] and "cv"."""
+    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts)
+
+    def phase_score(st):
+        return {**st, "mom": irm_score_moments(pan, st["coef"], clip, 2)}
+
+    def phase_final(st):
+        return {**st, "res": irm_finalize(st["mom"])}
+
+    phases.append(phase_score)
+    if reduce is not None:
+        phases.append(reduce("mom"))
+    phases.append(phase_final)
+    return phases
+
+
+def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None):
+    """The phases of :func:`irm_phases` up to the fitted coefficients (A, C01, B; state "G",
+    "cv", "coef"), shared with the group-effect estimator (estimators/gate.py), and the
+    factory ``reduce(name)`` of an all-reduce phase of a state tensor (None at world 1)."""
     from ..utils.graphs import Collective
     dist = comm is not None and comm.world_size > 1
     K = folds
@@ -168,12 +238,6 @@ def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_cou
         coef = (cv.coef_min if lambda_rule == "min" else cv.coef_1se).reshape(K, 3, -1)
         return {**st, "cv": cv, "coef": coef.double().contiguous()}
 
-    def phase_score(st):
-        return {**st, "mom": irm_score_moments(pan, st["coef"], clip, 2)}
-
-    def phase_final(st):
-        return {**st, "res": irm_finalize(st["mom"])}
-
     cap = bool(getattr(comm, "capturable", False))
 
     def reduce(name):
@@ -193,11 +257,8 @@ def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_cou
     phases = [phase_gram, phase_gram_reduce]
     if dist:
         phases.append(reduce_sym("G"))
-    phases += [phase_fit, phase_score]
-    if dist:
-        phases.append(reduce("mom"))
-    phases.append(phase_final)
-    return phases
+    phases.append(phase_fit)
+    return phases, (reduce if dist else None)
 
 
 def irm_crossfit_panel(pan, folds: int, lambda_rule="min", clip=0.01, comm=None,

@@ -31,6 +31,7 @@ P_DGP = 5           # synthetic data generation
 P_SUBSAMPLE = 6     # grf half-sampling / honesty split
 P_GBDT = 7          # GBDT row/feature subsampling
 P_SAMPLE_ROWS = 8   # sample_n row selection in the data pipeline
+P_MULT = 9          # Rademacher multipliers of the grouped multiplier bootstrap (csrc/gate.hip)
 
 
 def philox4x32(c0, c1, c2, c3, k0, k1, rounds: int = 10):
@@ -90,6 +91,24 @@ def normal_pair(seed: int, purpose: int, stream, index):
     u2 = np.floor(w[..., 1] / 256.0) * (1.0 / 16777216.0)
     r = np.sqrt(-2.0 * np.log(u1))
     return r * np.cos(2 * np.pi * u2), r * np.sin(2 * np.pi * u2)
+
+
+def rademacher(seed: int, index, n_boot: int) -> np.ndarray:
+    """Rademacher multipliers int8 [n, n_boot] of the rows with global ids ``index``:
+    replicate b of row i is bit b % 32 (LSB = 0) of word (b % 128) // 32 of
+    ``random_u32(seed, P_MULT, b // 128, i)``, +1 when set and -1 otherwise, so one Philox
+    call serves 128 replicates of a row (csrc/gate.hip reads the same bits). Keyed by the
+    global row id: the same draws at every world size and in every row order."""
+    index = np.asarray(index, dtype=np.uint64).reshape(-1)
+    n_boot = int(n_boot)
+    ns = -(-n_boot // 128)
+    out = np.empty((len(index), ns * 128), dtype=np.int8)
+    shifts = np.arange(32, dtype=np.uint32)
+    for s in range(ns):                      # one stream at a time: bounded temporaries
+        w = random_u32(seed, P_MULT, s, index)                        # (n, 4)
+        bits = (w[:, :, None] >> shifts) & np.uint32(1)               # (n, 4, 32)
+        out[:, s * 128:(s + 1) * 128] = bits.reshape(len(index), 128).astype(np.int8) * 2 - 1
+    return out[:, :n_boot]
 
 
 def fold_ids(n: int, k: int, seed: int, stream: int = 0) -> np.ndarray:

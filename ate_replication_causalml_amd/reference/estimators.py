@@ -347,16 +347,9 @@ def dml_plr_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min",
     return dml_from_residuals(yr, wr, method)
 
 
-def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
-                  method="DML-IRM cross-fit (LASSO)", fold_ids=None):
-    """Cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1) with
-    CV-LASSO nuisances, row by row in float64: for held-out fold k, g0 and g1 are gaussian
-    LASSO fits of Y on the training rows of each arm and m is the linear-probability LASSO of
-    W on all training rows, each with lambda chosen by (K-1)-fold CV over the training folds
-    (as dml_plr_lasso). Score (textbook signs): psi = g1 - g0 + W (Y - g1) / m
-    - (1 - W)(Y - g0) / (1 - m) with m clipped to [clip, 1 - clip]; theta = mean(psi),
-    SE = sd(psi) / sqrt(n)."""
-    Y, W, X = _arr(Y), _arr(W), _arr(X)
+def _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids=None):
+    """The held-out nuisances and per-row AIPW scores of the cross-fitted interactive model
+    (validated inputs as float64 arrays): (psi, g0, g1, m), m before clipping."""
     if not np.isin(W, (0.0, 1.0)).all():
         raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
     fid = rng.fold_ids(len(Y), folds, seed, stream=0) if fold_ids is None else \
@@ -378,6 +371,20 @@ def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
             out[te] = cv.predict(X[te], s=s)
     e = np.clip(m, clip, 1 - clip)
     psi = g1 - g0 + W * (Y - g1) / e - (1 - W) * (Y - g0) / (1 - e)
+    return psi, g0, g1, m
+
+
+def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                  method="DML-IRM cross-fit (LASSO)", fold_ids=None):
+    """Cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1) with
+    CV-LASSO nuisances, row by row in float64: for held-out fold k, g0 and g1 are gaussian
+    LASSO fits of Y on the training rows of each arm and m is the linear-probability LASSO of
+    W on all training rows, each with lambda chosen by (K-1)-fold CV over the training folds
+    (as dml_plr_lasso). Score (textbook signs): psi = g1 - g0 + W (Y - g1) / m
+    - (1 - W)(Y - g0) / (1 - m) with m clipped to [clip, 1 - clip]; theta = mean(psi),
+    SE = sd(psi) / sqrt(n)."""
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    psi, g0, g1, m = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
     n = len(Y)
     nt = W.sum()
     return AteResult.make(method, psi.mean(), psi.std(ddof=1) / np.sqrt(n), n=n,
@@ -386,6 +393,72 @@ def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
                           rmse_g0=float(np.sqrt(((1 - W) * (Y - g0) ** 2).sum() / (n - nt))),
                           rmse_g1=float(np.sqrt((W * (Y - g1) ** 2).sum() / nt)),
                           rmse_m=float(np.sqrt(((W - m) ** 2).mean())))
+
+
+def gate_from_scores(psi, codes, n_groups, n_boot=999, level=0.95, seed=1991, row_ids=None):
+    """Group means of per-row scores with the multiplier-bootstrap critical value of their
+    simultaneous band, in float64: theta_g = mean, SE_g = sd / sqrt(n_g), and with Rademacher
+    multipliers xi (rng.rademacher, keyed by ``row_ids``, default 0..n-1)
+    t[b, g] = S_{i in g} xi_i^b (psi_i - theta_g) / (n_g SE_g), crit = the
+    ceil(level n_boot)-th smallest of max_g |t[b, .]|.
+    Returns (n_g, theta, se, crit, A [B, G], Z [B, G]) with A = S xi psi, Z = S xi."""
+    from ..result import boot_rank
+    psi = np.asarray(psi, dtype=np.float64)
+    codes = np.asarray(codes, dtype=np.int64)
+    G, B = int(n_groups), int(n_boot)
+    rows = np.arange(len(psi)) if row_ids is None else np.asarray(row_ids)
+    xi = rng.rademacher(seed, rows, B)
+    ng = np.zeros(G)
+    theta = np.zeros(G)
+    se = np.zeros(G)
+    A = np.zeros((B, G))
+    Z = np.zeros((B, G), dtype=np.int64)
+    t = np.zeros((B, G))
+    for g in range(G):
+        in_g = codes == g
+        pg = psi[in_g]
+        ng[g] = len(pg)
+        theta[g] = pg.mean()
+        se[g] = pg.std(ddof=1) / np.sqrt(len(pg))
+        xg = xi[in_g].astype(np.float64)
+        A[:, g] = pg @ xg
+        Z[:, g] = xi[in_g].astype(np.int64).sum(axis=0)
+        t[:, g] = ((pg - theta[g]) @ xg) / (ng[g] * se[g])
+    crit = np.sort(np.abs(t).max(axis=1))[boot_rank(level, B) - 1]
+    return ng, theta, se, float(crit), A, Z
+
+
+def dml_irm_gate(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", clip=0.01, n_boot=999,
+                 level=0.95, method="DML-IRM group ATEs (LASSO)", fold_ids=None,
+                 keep_boot=False):
+    """Group average treatment effects of the cross-fitted interactive model with a
+    simultaneous confidence band (the float64 twin of estimators.gate.dml_irm_gate_lasso):
+    the scores of dml_irm_lasso, averaged within the groups of ``groups`` (one per distinct
+    label), and the Rademacher multiplier bootstrap of gate_from_scores."""
+    from ..result import GateResult, boot_rank
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    gl = np.asarray(groups)
+    if gl.ndim != 1 or len(gl) != len(Y):
+        raise ValueError(f"groups must be a vector with one label per row ({len(Y)}), "
+                         f"got shape {gl.shape}")
+    if int(n_boot) != n_boot or not 1 <= int(n_boot) <= 4096:
+        raise ValueError(f"n_boot must be an integer in [1, 4096], got {n_boot}")
+    boot_rank(level, int(n_boot))
+    labels, codes = np.unique(gl, return_inverse=True)
+    if len(labels) > 64:
+        raise ValueError(f"at most 64 groups are supported, got {len(labels)}")
+    for g, c in enumerate(np.bincount(codes, minlength=len(labels))):
+        if c < 2:
+            raise ValueError(f"group {g} has {int(c)} row(s): every group needs at least 2")
+    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    ng, theta, se, crit, A, Z = gate_from_scores(psi, codes, len(labels), n_boot, level, seed)
+    n = len(Y)
+    overall = AteResult.make("DML-IRM cross-fit (LASSO)", psi.mean(),
+                             psi.std(ddof=1) / np.sqrt(n), n=n)
+    res = GateResult.make(method, labels, ng, theta, se, crit, int(n_boot), level, overall)
+    if keep_boot:
+        res.boot = {"A": A, "Z": Z}
+    return res
 
 
 def dml_plr_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="min",

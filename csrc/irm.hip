@@ -9,7 +9,9 @@
 //   psi_i = g1_i - g0_i + w_i (y_i - g1_i) / e_i - (1 - w_i) (y_i - g0_i) / (1 - e_i)
 // and the 8 moments
 //   {S psi, S psi^2, n, n_clipped, S w (y - g1)^2, S (1 - w)(y - g0)^2, S (w - m)^2, n_treated}
-// are accumulated in fp64: no per-row value is written to HBM. w is read from the panel
+// are accumulated in fp64: no per-row value is written to HBM (ate_irm_score_moments), or,
+// by the same kernels instantiated with ROWS, psi_i itself is written per row for the group
+// bootstrap of csrc/gate.hip (ate_irm_scores). w is read from the panel
 // on every row, never inferred from the segment. Only the columns in the union of the three
 // LASSO supports are read, once each; the coefficient triple is staged in LDS. y / w are
 // rebuilt from their hi + lo bf16 columns on bf16 panels. Structure as csrc/dml.hip.
@@ -59,13 +61,21 @@ __device__ int compact_support3(C* c0, C* c1, C* cm, int* xc, int p, int* wcnt /
   return base;
 }
 
-// one valid row's contribution (everything after the three dot products, fp64)
+// the AIPW score of one valid row (everything after the three dot products, fp64)
+__device__ __forceinline__ double irm_psi(double y, double w, double g0, double g1, double m,
+                                          double clip) {
+  const double lo = clip, hi = 1.0 - clip;
+  const double e = m < lo ? lo : (m > hi ? hi : m);
+  const double r1 = y - g1, r0 = y - g0;
+  return g1 - g0 + w * r1 / e - (1.0 - w) * r0 / (1.0 - e);
+}
+
+// one valid row's contribution to the 8 moments
 __device__ __forceinline__ void irm_accumulate(double (&v)[NM], double y, double w, double g0,
                                                double g1, double m, double clip) {
   const double lo = clip, hi = 1.0 - clip;
-  const double e = m < lo ? lo : (m > hi ? hi : m);
   const double r1 = y - g1, r0 = y - g0, rm = w - m;
-  const double psi = g1 - g0 + w * r1 / e - (1.0 - w) * r0 / (1.0 - e);
+  const double psi = irm_psi(y, w, g0, g1, m, clip);
   v[0] += psi;
   v[1] += psi * psi;
   v[2] += 1.0;
@@ -85,8 +95,10 @@ __device__ __forceinline__ void write_partial(double (&v)[NM], double* red, doub
   }
 }
 
-// fp32 / fp64 column-major panels: fp64 dot products, RPT rows per thread 256 apart
-template <typename T, int RPT>
+// fp32 / fp64 column-major panels: fp64 dot products, RPT rows per thread 256 apart.
+// ROWS: `partial` is psi[ld] instead -- every row of the segment gets its score (0 on a
+// padding row) and no moment is accumulated (ate_irm_scores).
+template <typename T, int RPT, bool ROWS>
 __global__ __launch_bounds__(256) void irm_score_kernel(
     const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p, int P,
     const Seg* __restrict__ segs, int nseg, int spf,
@@ -141,19 +153,25 @@ __global__ __launch_bounds__(256) void irm_score_kernel(
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
       if (ii[r] >= sg.r1) continue;
-      if (ld_col(X, ld, vcol, ii[r]) == 0.0) continue;          // padding row
+      if (ld_col(X, ld, vcol, ii[r]) == 0.0) {                  // padding row
+        if (ROWS) partial[ii[r]] = 0.0;
+        continue;
+      }
       const double y = ld_col(X, ld, y0, ii[r]) + (y1 >= 0 ? ld_col(X, ld, y1, ii[r]) : 0.0);
       const double w = ld_col(X, ld, w0, ii[r]) + (w1 >= 0 ? ld_col(X, ld, w1, ii[r]) : 0.0);
       ATE_DASSERT(spf != 2 || w == (double)(s & 1));
-      irm_accumulate(v, y, w, a0[r], a1[r], am[r], clip);
+      if (ROWS) partial[ii[r]] = irm_psi(y, w, a0[r], a1[r], am[r], clip);
+      else irm_accumulate(v, y, w, a0[r], a1[r], am[r], clip);
     }
   }
-  write_partial(v, red, partial);
+  if (!ROWS) write_partial(v, red, partial);
 }
 
 // bf16 panels: each thread owns 8 CONSECUTIVE rows, so every column read is one 16-byte
 // load through (cs, bs) (column-major and 64-row blocked panels); dot products in fp32
 // (bf16 values are exact in fp32; coefficients rounded to fp32), the score in fp64.
+// ROWS: as irm_score_kernel.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void irm_score_bf16_kernel(
     const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
     int P, int64_t ld, const Seg* __restrict__ segs, int nseg, int spf,
@@ -216,14 +234,18 @@ __global__ __launch_bounds__(256) void irm_score_bf16_kernel(
     if (w1 >= 0) ld8(w1, i, wb); else { for (int r = 0; r < 8; ++r) wb[r] = 0.f; }
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-      if (vv[r] == 0.f) continue;                                 // padding row
+      if (vv[r] == 0.f) {                                         // padding row
+        if (ROWS) partial[i + r] = 0.0;
+        continue;
+      }
       const double y = (double)ya[r] + (double)yb[r];
       const double w = (double)wa[r] + (double)wb[r];
       ATE_DASSERT(spf != 2 || w == (double)(s & 1));
-      irm_accumulate(v, y, w, (double)a0[r], (double)a1[r], (double)am[r], clip);
+      if (ROWS) partial[i + r] = irm_psi(y, w, (double)a0[r], (double)a1[r], (double)am[r], clip);
+      else irm_accumulate(v, y, w, (double)a0[r], (double)a1[r], (double)am[r], clip);
     }
   }
-  write_partial(v, red, partial);
+  if (!ROWS) write_partial(v, red, partial);
 }
 
 // one block of 256 threads: thread i sums partials i, i+256, ... (fixed order), then a
@@ -242,13 +264,44 @@ __global__ __launch_bounds__(256) void irm_sum_kernel(const double* __restrict__
     for (int q = 0; q < NM; ++q) out[q] = v[q];
 }
 
-template <typename T>
+template <typename T, bool ROWS>
 int irm_score_t(const void* X, int64_t ld, const void* xcols, int p, int P, const void* segs,
                 int nseg, int spf, const void* coef, int y0, int y1, int w0, int w1, int vcol,
                 double clip, int nbx, void* partial, size_t sh, hipStream_t s) {
-  ATE_LAUNCH((irm_score_kernel<T, 4>), dim3(nbx, nseg), dim3(256), sh, s, (const T*)X, ld,
+  ATE_LAUNCH((irm_score_kernel<T, 4, ROWS>), dim3(nbx, nseg), dim3(256), sh, s, (const T*)X, ld,
              (const int*)xcols, p, P, (const Seg*)segs, nseg, spf, (const double*)coef, y0, y1,
              w0, w1, vcol, clip, (double*)partial);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The score pass of both entry points (argument checks and the launch): ROWS writes psi[ld]
+// through `out`, otherwise `out` is the partial buffer [nseg*nbx][8] of the moment pass.
+template <bool ROWS>
+int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols, int p,
+             const void* segs, int nseg, int segs_per_fold, const void* coef, int y0, int y1,
+             int w0, int w1, int vcol, double clip, int nbx, void* out, hipStream_t s) {
+  if (dtype < 1 || dtype > 3 || (dtype != 3 && bs != 64)) return -1;
+  if (p < 0 || nseg < 1 || nseg > 65535 || segs_per_fold < 1 || nbx < 1 || cs < 64 || bs < 64)
+    return -1;
+  if (y0 < 0 || w0 < 0 || vcol < 0) return -1;
+  // what the strides say about the panel's extent, for the debug build's bounds checks
+  // (0 = unknown): column-major (bs = 64) has ld = cs rows; 64-row blocked has P = bs / 64
+  const int64_t ld = bs == 64 ? cs : 0;
+  const int P = bs == 64 ? 0 : (int)(bs / 64);
+  if (!(clip >= 0.0 && clip < 0.5)) return -1;
+  const size_t esz = dtype == 3 ? sizeof(float) : sizeof(double);
+  const size_t sh = (size_t)3 * (p + 1) * esz + (size_t)p * sizeof(int);
+  if (sh > 64 * 1024 - 2048) return -1;     // dynamic + static LDS within the 64 KB default
+  if (dtype == 1)
+    return irm_score_t<float, ROWS>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
+                                    w0, w1, vcol, clip, nbx, out, sh, s);
+  if (dtype == 2)
+    return irm_score_t<double, ROWS>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
+                                     w0, w1, vcol, clip, nbx, out, sh, s);
+  ATE_LAUNCH(irm_score_bf16_kernel<ROWS>, dim3(nbx, nseg), dim3(256), sh, s, (const bf16_t*)X, cs,
+             bs, (const int*)xcols, p, P, ld, (const Seg*)segs, nseg, segs_per_fold,
+             (const double*)coef, y0, y1, w0, w1, vcol, clip, (double*)out);
   ATE_CHECK_LAUNCH();
   return 0;
 }
@@ -265,35 +318,22 @@ ATE_API int ate_irm_score_moments(int dtype, const void* X, int64_t cs, int64_t 
                                   int w1, int vcol, double clip, int nbx, void* partial,
                                   void* moments, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (dtype < 1 || dtype > 3 || (dtype != 3 && bs != 64)) return -1;
-  if (p < 0 || nseg < 1 || nseg > 65535 || segs_per_fold < 1 || nbx < 1 || cs < 64 || bs < 64)
-    return -1;
-  if (y0 < 0 || w0 < 0 || vcol < 0) return -1;
-  // what the strides say about the panel's extent, for the debug build's bounds checks
-  // (0 = unknown): column-major (bs = 64) has ld = cs rows; 64-row blocked has P = bs / 64
-  const int64_t ld = bs == 64 ? cs : 0;
-  const int P = bs == 64 ? 0 : (int)(bs / 64);
-  if (!(clip >= 0.0 && clip < 0.5)) return -1;
-  const size_t esz = dtype == 3 ? sizeof(float) : sizeof(double);
-  const size_t sh = (size_t)3 * (p + 1) * esz + (size_t)p * sizeof(int);
-  if (sh > 64 * 1024 - 2048) return -1;     // dynamic + static LDS within the 64 KB default
-  int rc = -1;
-  if (dtype == 1)
-    rc = irm_score_t<float>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1, w0, w1,
-                            vcol, clip, nbx, partial, sh, s);
-  else if (dtype == 2)
-    rc = irm_score_t<double>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1, w0, w1,
-                             vcol, clip, nbx, partial, sh, s);
-  else {
-    ATE_LAUNCH(irm_score_bf16_kernel, dim3(nbx, nseg), dim3(256), sh, s, (const bf16_t*)X, cs, bs,
-               (const int*)xcols, p, P, ld, (const Seg*)segs, nseg, segs_per_fold,
-               (const double*)coef, y0, y1, w0, w1, vcol, clip, (double*)partial);
-    ATE_CHECK_LAUNCH();
-    rc = 0;
-  }
+  const int rc = irm_pass<false>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0,
+                                 y1, w0, w1, vcol, clip, nbx, partial, s);
   if (rc != 0) return rc;
   ATE_LAUNCH(irm_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
              (double*)moments);
   ATE_CHECK_LAUNCH();
   return 0;
+}
+
+// The same pass, same arguments and dot products, writing the per-row scores instead:
+// psi [ld] fp64 in panel row order, 0 on padding rows. Every row inside a segment is
+// written; the segments of a panel tile [0, ld).
+ATE_API int ate_irm_scores(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols,
+                           int p, const void* segs, int nseg, int segs_per_fold,
+                           const void* coef, int y0, int y1, int w0, int w1, int vcol,
+                           double clip, int nbx, void* psi, void* stream) {
+  return irm_pass<true>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0, y1, w0,
+                        w1, vcol, clip, nbx, psi, (hipStream_t)stream);
 }
