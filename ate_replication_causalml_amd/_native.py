@@ -100,6 +100,7 @@ _SIGS = {
     "ate_dml_resid_exact": "pllpipipiiiiiiippp",
     "ate_irm_score_moments": "ipllpipiipiiiiidippp",
     "ate_irm_scores": "ipllpipiipiiiiidipp",
+    "ate_irm_sens_moments": "ipllpipiipiiiiidippp",
     "ate_group_boot": "pppliiuippp",
     "ate_group_boot_scratch": "iii",
     "ate_lognet_path": "iplpiipipipdddippippppppppp",

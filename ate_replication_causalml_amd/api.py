@@ -18,7 +18,9 @@ doubly_robust_glm -> ate_aipw_glm; belloni -> ate_belloni; double_ml ->
 ate_double_ml; residual_balance_ATE -> ate_residual_balance; grf::causal_forest +
 estimate_average_effect -> ate_causal_forest; K-fold DML-PLR -> ate_dml; K-fold DML-IRM
 (cross-fitted AIPW, LASSO nuisances) -> ate_dml_irm; its group effects with a joint
-multiplier-bootstrap band (DoubleML gate / bootstrap / confint(joint=True)) -> ate_dml_irm_gate.
+multiplier-bootstrap band (DoubleML gate / bootstrap / confint(joint=True)) -> ate_dml_irm_gate;
+its sensitivity to unobserved confounding (DoubleML sensitivity_analysis /
+sensitivity_benchmark) -> ate_dml_irm_sensitivity.
 """
 from __future__ import annotations
 
@@ -28,7 +30,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import AteResult, GateResult, format_table, results_frame
+from .result import AteResult, GateResult, SensitivityResult, format_table, results_frame
 from .utils import guards
 from .utils.tracing import trace
 
@@ -269,6 +271,28 @@ def ate_dml_irm_gate(Y, W, X, groups, folds=5, lambda_rule="min", clip=0.01, n_b
                                      dtype=run.dtype)
 
 
+def ate_dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0,
+                            benchmarks=None, folds=5, lambda_rule="min", clip=0.01,
+                            run=None) -> SensitivityResult:
+    """Sensitivity of ate_dml_irm to unobserved confounding (Chernozhukov, Cinelli, Newey,
+    Sharma & Syrgkanis 2022; DoubleML sensitivity_analysis / sensitivity_benchmark): bounds on
+    the ATE and their one-sided ``level`` CI under a confounder of strength (cf_y, cf_d,
+    rho), the robustness values RV / RVa against ``null``, and the strength of each covariate
+    set of ``benchmarks`` (lists of column indices into X, at most 8), from a refit without
+    it (estimators/sensitivity.py). Further scenarios: ``result.bounds(cf_y, cf_d, rho)``."""
+    run = _run(run)
+    with trace("ate_dml_irm_sensitivity", folds=folds):
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_irm_sensitivity(Y, W, X, cf_y, cf_d, rho, level, null, benchmarks,
+                                         folds=folds, seed=run.seed, lambda_rule=lambda_rule,
+                                         clip=clip)
+        from .estimators import sensitivity as DS
+        return DS.dml_irm_sensitivity(Y, W, X, cf_y, cf_d, rho, level, null, benchmarks,
+                                      folds=folds, seed=run.seed, lambda_rule=lambda_rule,
+                                      clip=clip, device=run.device(), dtype=run.dtype)
+
+
 def ate_residual_balance(Y, W, X, balance: BalanceConfig | None = None,
                          method="residual_balancing", run=None) -> AteResult:
     """E14 residual_balance_ATE (ate_functions.R:393-405) -> balanceHD::residualBalance.ate."""
@@ -442,7 +466,7 @@ def replicate(data=None, config: ReplicateConfig | None = None, log_path=None, p
 __all__ = [
     "ate_naive", "ate_ols", "propensity_logistic", "propensity_lasso", "ate_ipw", "ate_ipw_wls",
     "ate_lasso_single", "ate_lasso", "ate_aipw_rf", "ate_aipw_glm", "ate_belloni",
-    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_residual_balance", "ate_causal_forest", "replicate",
+    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_sensitivity", "ate_residual_balance", "ate_causal_forest", "replicate",
     "ate_aipw_crossfit", "ate_causal_forest_bootstrap",
-    "Replication", "AteResult", "GateResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
+    "Replication", "AteResult", "GateResult", "SensitivityResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
 ]

@@ -48,6 +48,8 @@ def _dml(a):
             raise SystemExit("--model irm has no repeated cross-fitting")
         pan = synthetic_panel(a.n, p=a.p, folds=a.folds, seed=a.seed, dtype=a.dtype, device=dev,
                               arm_split=True)
+        if a.gate_col is not None and a.sensitivity:
+            raise SystemExit("--gate-col and --sensitivity are separate analyses: pick one")
         if a.gate_col is not None:
             # group effects over quantile bins of covariate x{gate_col}, with a joint band
             from .estimators.gate import irm_gate_panel, quantile_groups
@@ -63,6 +65,27 @@ def _dml(a):
                                                v[3 * G + 2], n=a.n))
             out = {"groups": r.rows(), "crit": r.crit, "n_boot": r.n_boot, "level": r.level,
                    "edges": edges.cpu().tolist(), "ate": r.overall.ate, "se": r.overall.se}
+            print(json.dumps(out))
+            return 0
+        if a.sensitivity:
+            # bounds under a confounder of strength (cf_y, cf_d, rho), RV / RVa, benchmarks
+            from dataclasses import asdict
+            from .estimators.sensitivity import irm_sens_panel
+            from .result import SensitivityResult, check_benchmarks, check_scenario
+            check_scenario(a.cf_y, a.cf_d, a.rho)
+            try:
+                sets = [[int(c) for c in s.split(",")] for s in a.benchmark_cols or []]
+            except ValueError:
+                raise SystemExit("--benchmark-cols takes comma-separated column indices")
+            bench = check_benchmarks(sets or None, a.p)
+            mom, _ = irm_sens_panel(pan, a.folds, a.lambda_rule, a.clip, bench)
+            v = mom.double().cpu().numpy()
+            r = SensitivityResult.from_moments(
+                "DML-IRM sensitivity (LASSO)", v[0], a.cf_y, a.cf_d, a.rho, 0.95, a.null,
+                short=[(cols, v[1 + j]) for j, cols in enumerate(bench)], n=a.n)
+            out = {"ate": r.theta, "se": r.se, "sigma2": r.sigma2, "nu2": r.nu2,
+                   **{k: val for k, val in asdict(r.scenario).items()}, "null": r.null,
+                   "rv": r.rv, "rva": r.rva, "benchmarks": [asdict(b) for b in r.benchmarks]}
             print(json.dumps(out))
             return 0
         res, mom, cv = irm_crossfit_panel(pan, a.folds, a.lambda_rule, a.clip)
@@ -135,6 +158,16 @@ def main(argv=None):
     d.add_argument("--gate-bins", type=int, default=4, help="irm --gate-col: quantile groups")
     d.add_argument("--boot", type=int, default=999,
                    help="irm --gate-col: multiplier-bootstrap draws of the joint band")
+    d.add_argument("--sensitivity", action="store_true",
+                   help="irm: bounds under unobserved confounding, robustness values")
+    d.add_argument("--cf-y", type=float, default=0.03, help="irm --sensitivity: outcome strength")
+    d.add_argument("--cf-d", type=float, default=0.03,
+                   help="irm --sensitivity: treatment (Riesz representer) strength")
+    d.add_argument("--rho", type=float, default=1.0, help="irm --sensitivity: bias correlation")
+    d.add_argument("--null", type=float, default=0.0,
+                   help="irm --sensitivity: the hypothesis of the robustness values")
+    d.add_argument("--benchmark-cols", action="append", metavar="J,J,...",
+                   help="irm --sensitivity: benchmark the covariate set x{J}, ... (repeatable)")
     d.set_defaults(fn=_dml)
     b = sub.add_parser("build")
     b.set_defaults(fn=_build)

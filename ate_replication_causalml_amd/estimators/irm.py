@@ -201,6 +201,22 @@ def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_cou
     return phases
 
 
+def fit_problems(pan, K: int, counts):
+    """The 3 K nuisance problems on the 3K-Gram stack ``cat([G, G[0::2] + G[1::2]])`` as
+    arguments of ``cv_enet_gaussian``: (seg_counts, full_sets, full_y, ycols). Segments of
+    the stack: 2s + a = (fold s, arm a); 2K + s = fold s, both arms. ``counts``: (global)
+    rows per panel segment."""
+    counts = np.asarray(counts, dtype=np.float64)
+    counts3 = np.concatenate([counts, counts[0::2] + counts[1::2]])
+    full_sets, full_y = [], []
+    for k in range(K):
+        others = [s for s in range(K) if s != k]
+        full_sets += [[2 * s for s in others], [2 * s + 1 for s in others],
+                      [2 * K + s for s in others]]
+        full_y += [0, 0, 1]                       # g0, g1: target Y; m: target W
+    return counts3, full_sets, full_y, [pan.cols["Y"], pan.cols["W"]]
+
+
 def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None):
     """The phases of :func:`irm_phases` up to the fitted coefficients (A, C01, B; state "G",
     "cv", "coef"), shared with the group-effect estimator (estimators/gate.py), and the
@@ -214,15 +230,7 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
     check_cells(counts, K)
     if pan.nseg != 2 * K:
         raise ValueError(f"DML-IRM needs {2 * K} segments, this shard's panel has {pan.nseg}")
-    # segments of the 3K-Gram stack: 2s + a = (fold s, arm a); 2K + s = fold s, both arms
-    counts3 = np.concatenate([counts, counts[0::2] + counts[1::2]])
-    full_sets, full_y = [], []
-    for k in range(K):
-        others = [s for s in range(K) if s != k]
-        full_sets += [[2 * s for s in others], [2 * s + 1 for s in others],
-                      [2 * K + s for s in others]]
-        full_y += [0, 0, 1]                       # g0, g1: target Y; m: target W
-    ycols = [pan.cols["Y"], pan.cols["W"]]
+    counts3, full_sets, full_y, ycols = fit_problems(pan, K, counts)
 
     def phase_gram(_):
         return {"G": gram(pan, stage="tiles")}

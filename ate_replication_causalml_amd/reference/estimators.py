@@ -461,6 +461,109 @@ def dml_irm_gate(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", clip=0.
     return res
 
 
+def sensitivity_from_rows(psi, b, c, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0):
+    """The sensitivity figures of per-row (psi, b, c), row by row in float64 -- written
+    independently of the moment route of result.SensitivityResult: the SEs are
+    np.std(ddof=1) of the bound's influence function psi - theta -/+ k pmb, and RV / RVa
+    are found by bisection on cf. Returns (theta, se, sigma2, nu2, SensBounds, rv, rva)."""
+    from statistics import NormalDist
+    from ..result import SensBounds, check_scenario
+    from ..utils.guards import NumericalError
+    check_scenario(cf_y, cf_d, rho, level)
+    psi, b, c = (np.asarray(v, dtype=np.float64) for v in (psi, b, c))
+    n = len(psi)
+    theta, sigma2, nu2 = psi.mean(), b.mean(), c.mean()
+    if not (sigma2 > 0 and nu2 > 0):
+        raise NumericalError(f"sensitivity analysis needs sigma2 > 0 and nu2 > 0, got "
+                             f"sigma2 = {sigma2}, nu2 = {nu2}")
+    S = np.sqrt(sigma2 * nu2)
+    pmb = (sigma2 * (c - nu2) + nu2 * (b - sigma2)) / (2 * S)
+    z = NormalDist().inv_cdf(level)
+
+    def at(cy, cd, r=rho):
+        k = abs(r) * np.sqrt(cy) * np.sqrt(cd / (1 - cd))
+        lo, hi = theta - S * k, theta + S * k
+        se_lo = (psi - theta - k * pmb).std(ddof=1) / np.sqrt(n)
+        se_hi = (psi - theta + k * pmb).std(ddof=1) / np.sqrt(n)
+        return SensBounds(float(cy), float(cd), float(r), float(level), float(lo), float(hi),
+                          float(se_lo), float(se_hi), float(lo - z * se_lo),
+                          float(hi + z * se_hi))
+
+    up = theta >= null
+
+    def gap(cf, ci):
+        """Signed distance from the (confidence) bound on the null's side to the null."""
+        s = at(cf, cf)
+        if up:
+            return (s.ci_lower if ci else s.theta_lower) - null
+        return null - (s.ci_upper if ci else s.theta_upper)
+
+    def root(ci):
+        if gap(0.0, ci) <= 0:
+            return 0.0
+        lo, hi = 0.0, 1.0 - 2.0 ** -40
+        if gap(hi, ci) > 0:
+            return 1.0
+        for _ in range(200):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if gap(mid, ci) > 0 else (lo, mid)
+        return 0.5 * (lo + hi)
+
+    return (float(theta), float(psi.std(ddof=1) / np.sqrt(n)), float(sigma2), float(nu2),
+            at(cf_y, cf_d), root(False), root(True))
+
+
+def _sens_rows(Y, W, X, folds, seed, lambda_rule, clip, fold_ids=None):
+    """(psi, b, c, m) per row of the cross-fitted interactive model, m before clipping."""
+    psi, g0, g1, m = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    e = np.clip(m, clip, 1 - clip)
+    b = (Y - np.where(W == 1, g1, g0)) ** 2
+    rr = W / e - (1 - W) / (1 - e)
+    c = 2 * (1 / e + 1 / (1 - e)) - rr ** 2
+    return psi, b, c, m
+
+
+def dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0,
+                        benchmarks=None, folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                        method="DML-IRM sensitivity (LASSO)", fold_ids=None):
+    """Sensitivity of the cross-fitted IRM's ATE to unobserved confounding (Chernozhukov,
+    Cinelli, Newey, Sharma & Syrgkanis 2022), the float64 twin of
+    estimators.sensitivity.dml_irm_sensitivity: per-row arrays from _irm_scores,
+    sensitivity_from_rows for the bounds and robustness values, and for every benchmark set
+    a second _irm_scores run on the other columns (same folds, same clip)."""
+    from ..result import SensBenchmark, SensitivityResult, check_benchmarks, check_scenario
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    check_scenario(cf_y, cf_d, rho, level)
+    bench = check_benchmarks(benchmarks, X.shape[1])
+    psi, b, c, m = _sens_rows(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    theta, se, sigma2, nu2, scen, rv, rva = sensitivity_from_rows(psi, b, c, cf_y, cf_d, rho,
+                                                                  level, null)
+    n = len(Y)
+    rows = []
+    var_y = Y.var()
+    for cols in bench:
+        kept = [j for j in range(X.shape[1]) if j not in cols]
+        ps, bs, cs, _ = _sens_rows(Y, W, X[:, kept], folds, seed, lambda_rule, clip, fold_ids)
+        th_s, s2_s, nu_s = ps.mean(), bs.mean(), cs.mean()
+        r2_long, r2_short = 1 - sigma2 / var_y, 1 - s2_s / var_y
+        cy_raw = (r2_long - r2_short) / (1 - r2_long)
+        cd_raw = (nu2 - nu_s) / nu_s
+        delta = th_s - theta
+        var_g, var_riesz = s2_s - sigma2, nu2 - nu_s
+        r = float(np.sign(delta) * min(abs(delta) / np.sqrt(var_g * var_riesz), 1.0)) \
+            if var_g > 0 and var_riesz > 0 else float("nan")
+        rows.append(SensBenchmark(cols, float(np.clip(cy_raw, 0, 1)), float(np.clip(cd_raw, 0, 1)),
+                                  r, float(delta), float(cy_raw), float(cd_raw), float(th_s),
+                                  float(s2_s), float(nu_s)))
+    one = np.ones(n)
+    out = ((m < clip) | (m > 1 - clip)).astype(np.float64)
+    mom = [v.sum() for v in (psi, psi * psi, one, out, b, b * b, c, c * c, psi * b, psi * c,
+                             b * c, Y, Y * Y, W)]
+    diag = dict(n=n, n_clipped=int(out.sum()), n_treated=int(W.sum()))
+    return SensitivityResult(method, [float(v) for v in mom], theta, se, sigma2, nu2, scen,
+                             float(null), rv, rva, rows, diag)
+
+
 def dml_plr_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="min",
                            aggregate="median", method="DML cross-fit (LASSO, repeated)"):
     """Repeated cross-fitting (Chernozhukov et al. 2018 §3.4, median method): S = repeats

@@ -109,6 +109,279 @@ class GateResult:
                            "diagnostics": keep(self.diagnostics)}, default=str)
 
 
+# ------------------------------------------------------------ sensitivity to confounding
+# the 14 moments of the sensitivity pass (estimators/sensitivity.py, csrc/irm.hip), with
+# b = (y - g_w)^2, rr = w / e - (1 - w) / (1 - e), c = 2 (1 / e + 1 / (1 - e)) - rr^2
+SENS_MOMENTS = ("S psi", "S psi^2", "n", "n_clipped", "S b", "S b^2", "S c", "S c^2", "S psi b",
+                "S psi c", "S b c", "S y", "S y^2", "n_treated")
+N_BENCHMARKS_MAX = 8
+
+
+def check_scenario(cf_y, cf_d, rho=1.0, level=0.95):
+    """A confounding scenario: 0 <= cf_y < 1, 0 <= cf_d < 1, |rho| <= 1, 0.5 < level < 1."""
+    if not 0.0 <= cf_y < 1.0:
+        raise ValueError(f"cf_y must be in [0, 1), got {cf_y}")
+    if not 0.0 <= cf_d < 1.0:
+        raise ValueError(f"cf_d must be in [0, 1), got {cf_d}")
+    if not abs(rho) <= 1.0:
+        raise ValueError(f"rho must be in [-1, 1], got {rho}")
+    if not 0.5 < level < 1.0:
+        raise ValueError(f"level must be in (0.5, 1), got {level}")
+
+
+def check_benchmarks(benchmarks, p: int):
+    """Benchmark covariate sets as a tuple of tuples of column indices into X: at most 8
+    sets, each of distinct indices in [0, p) and not all of X. A flat list of integers is
+    one set."""
+    if benchmarks is None:
+        return ()
+    sets = list(benchmarks)
+    if sets and all(isinstance(c, (int,)) or (hasattr(c, "ndim") and c.ndim == 0) for c in sets):
+        sets = [sets]
+    if len(sets) > N_BENCHMARKS_MAX:
+        raise ValueError(f"at most {N_BENCHMARKS_MAX} benchmark sets per call, got {len(sets)}")
+    out = []
+    for cols in sets:
+        cols = [c for c in cols]
+        if any(int(c) != c for c in cols):
+            raise ValueError(f"benchmark columns must be integers, got {cols}")
+        cols = tuple(int(c) for c in cols)
+        if not cols:
+            raise ValueError("an empty benchmark set")
+        if any(not 0 <= c < p for c in cols):
+            raise ValueError(f"benchmark columns must index the {p} columns of X, got {cols}")
+        if len(set(cols)) != len(cols):
+            raise ValueError(f"benchmark columns must be distinct, got {cols}")
+        if len(cols) == p:
+            raise ValueError("a benchmark set must leave at least one column of X in the model")
+        out.append(cols)
+    return tuple(out)
+
+
+def cf_of_strength(a: float) -> float:
+    """The cf = cf_y = cf_d with cf / sqrt(1 - cf) = a >= 0:
+    (-a^2 + sqrt(a^4 + 4 a^2)) / 2, in the form without cancellation."""
+    if not a > 0.0:
+        return 0.0 if a == 0.0 else float("nan")
+    if math.isinf(a):
+        return 1.0
+    return 2.0 / (1.0 + math.sqrt(1.0 + 4.0 / (a * a)))
+
+
+def normal_quantile(level: float) -> float:
+    from statistics import NormalDist
+    return NormalDist().inv_cdf(level)
+
+
+@dataclass
+class SensBounds:
+    """One confounding scenario: the bounds on theta and their one-sided ``level`` CI."""
+    cf_y: float
+    cf_d: float
+    rho: float
+    level: float
+    theta_lower: float
+    theta_upper: float
+    se_lower: float
+    se_upper: float
+    ci_lower: float
+    ci_upper: float
+
+
+@dataclass
+class SensBenchmark:
+    """What leaving the covariate set ``columns`` out of the model does: the gains in
+    explanatory power of the outcome regression (cf_y) and of the Riesz representer (cf_d)
+    that these columns bring, raw and clipped to [0, 1], and the implied rho."""
+    columns: tuple
+    cf_y: float
+    cf_d: float
+    rho: float
+    delta_theta: float
+    cf_y_raw: float
+    cf_d_raw: float
+    theta_short: float
+    sigma2_short: float
+    nu2_short: float
+
+
+def sens_plugins(mom):
+    """(n, theta, sigma2, nu2, V11, V12, V22) from the 14 moments, float64 on the host.
+    V11 = var(psi), V22 = var(pmb), V12 = cov(psi, pmb) with
+    pmb = (sigma2 (c - nu2) + nu2 (b - sigma2)) / (2 S), S = sqrt(sigma2 nu2): linear in
+    (b, c), so all three come from the 3x3 covariance of (psi, b, c); the n - 1, centred
+    convention and the operation order of ``estimators.irm.irm_finalize``."""
+    m = [float(v) for v in mom]
+    if len(m) != len(SENS_MOMENTS):
+        raise ValueError(f"{len(SENS_MOMENTS)} moments expected, got {len(m)}")
+    n = m[2]
+    theta, sigma2, nu2 = m[0] / n, m[4] / n, m[6] / n
+    if not (sigma2 > 0.0 and nu2 > 0.0):
+        from .utils.guards import NumericalError
+        raise NumericalError(f"sensitivity analysis needs sigma2 > 0 and nu2 > 0, got "
+                             f"sigma2 = {sigma2}, nu2 = {nu2}")
+
+    def cov(suv, su, sv):
+        return (suv - su * sv / n) / (n - 1)
+
+    v11 = max(cov(m[1], m[0], m[0]), 0.0)
+    vb, vc, cbc = max(cov(m[5], m[4], m[4]), 0.0), max(cov(m[7], m[6], m[6]), 0.0), \
+        cov(m[10], m[4], m[6])
+    cpb, cpc = cov(m[8], m[0], m[4]), cov(m[9], m[0], m[6])
+    s = math.sqrt(sigma2 * nu2)
+    ab, ac = nu2 / (2.0 * s), sigma2 / (2.0 * s)
+    v22 = max(ab * ab * vb + ac * ac * vc + 2.0 * ab * ac * cbc, 0.0)
+    v12 = ab * cpb + ac * cpc
+    return n, theta, sigma2, nu2, v11, v12, v22
+
+
+def sens_bounds(mom, cf_y, cf_d, rho=1.0, level=0.95) -> SensBounds:
+    check_scenario(cf_y, cf_d, rho, level)
+    n, theta, sigma2, nu2, v11, v12, v22 = sens_plugins(mom)
+    s = math.sqrt(sigma2 * nu2)
+    k = abs(rho) * math.sqrt(cf_y) * math.sqrt(cf_d / (1.0 - cf_d))
+    z = normal_quantile(level)
+    lo, hi = theta - s * k, theta + s * k
+    se_lo = math.sqrt(max(v11 - 2.0 * k * v12 + k * k * v22, 0.0) / n)
+    se_hi = math.sqrt(max(v11 + 2.0 * k * v12 + k * k * v22, 0.0) / n)
+    return SensBounds(float(cf_y), float(cf_d), float(rho), float(level), lo, hi, se_lo, se_hi,
+                      lo - z * se_lo, hi + z * se_hi)
+
+
+def sens_robustness(mom, rho=1.0, level=0.95, null=0.0):
+    """(RV, RVa): the cf = cf_y = cf_d at which the bound on the side of ``null`` (RVa: its
+    confidence bound) reaches it. RVa is 0 when the CI at strength 0 covers the null."""
+    check_scenario(0.0, 0.0, rho, level)
+    n, theta, sigma2, nu2, v11, v12, v22 = sens_plugins(mom)
+    s = math.sqrt(sigma2 * nu2)
+    d = abs(theta - null)
+    r = abs(rho)
+    rv = cf_of_strength(d / (r * s)) if r > 0 else (1.0 if d > 0 else 0.0)
+    z = normal_quantile(level)
+    sgn = 1.0 if theta >= null else -1.0       # lower bound above, upper bound below the null
+    if d - z * math.sqrt(v11 / n) <= 0.0:
+        return rv, 0.0
+    # the smallest k in [0, D / S] with D - S k = z se(k), se(k)^2 = (V11 - 2 sgn k V12 +
+    # k^2 V22) / n: squared, A k^2 + B k + C = 0 with C > 0 here. D - S k - z se(k) is
+    # concave in k, positive at 0 and <= 0 at D / S: one root in the interval
+    zz = z * z / n
+    A = s * s - zz * v22
+    B = -2.0 * d * s + 2.0 * sgn * zz * v12
+    C = d * d - zz * v11
+    kmax = d / s
+    roots = []
+    if A == 0.0:
+        if B != 0.0:
+            roots.append(-C / B)
+    else:
+        disc = B * B - 4.0 * A * C
+        if disc >= 0.0:
+            q = -0.5 * (B + math.copysign(math.sqrt(disc), B))
+            roots += [q / A] + ([C / q] if q != 0.0 else [])
+    roots = [k for k in roots if 0.0 <= k <= kmax * (1.0 + 1e-12)]
+    if roots:
+        k = min(roots)
+    else:                                      # bisection on the unsquared equation
+        f = lambda k: d - s * k - z * math.sqrt(max(v11 - 2.0 * sgn * k * v12 + k * k * v22,
+                                                    0.0) / n)
+        a, b = 0.0, kmax
+        for _ in range(200):
+            k = 0.5 * (a + b)
+            a, b = (k, b) if f(k) > 0.0 else (a, k)
+        k = 0.5 * (a + b)
+    rva = cf_of_strength(k / r) if r > 0 else 1.0
+    return rv, rva
+
+
+def sens_benchmark(columns, mom_long, mom_short) -> SensBenchmark:
+    nl, th_l, s2_l, nu_l = sens_plugins(mom_long)[:4]
+    ns, th_s, s2_s, nu_s = sens_plugins(mom_short)[:4]
+    ml = [float(v) for v in mom_long]
+    var_y = ml[12] / nl - (ml[11] / nl) ** 2
+    r2_long, r2_short = 1.0 - s2_l / var_y, 1.0 - s2_s / var_y
+    cf_y_raw = (r2_long - r2_short) / (1.0 - r2_long)
+    cf_d_raw = (nu_l - nu_s) / nu_s
+    delta = th_s - th_l
+    var_g, var_riesz = s2_s - s2_l, nu_l - nu_s
+    if var_g > 0.0 and var_riesz > 0.0:
+        rho = math.copysign(min(abs(delta) / math.sqrt(var_g * var_riesz), 1.0), delta) \
+            if delta != 0.0 else 0.0
+    else:
+        rho = float("nan")
+    clip01 = lambda v: min(max(v, 0.0), 1.0)
+    return SensBenchmark(tuple(int(c) for c in columns), clip01(cf_y_raw), clip01(cf_d_raw), rho,
+                         delta, cf_y_raw, cf_d_raw, th_s, s2_s, nu_s)
+
+
+@dataclass
+class SensitivityResult:
+    """Sensitivity of the cross-fitted IRM's ATE to unobserved confounding (Chernozhukov,
+    Cinelli, Newey, Sharma & Syrgkanis 2022; DoubleML ``sensitivity_analysis`` /
+    ``sensitivity_benchmark``): the bounds of the default scenario, the robustness values
+    and the covariate benchmarks. Everything is a function of ``moments`` (SENS_MOMENTS), so
+    ``bounds()`` evaluates any further scenario on the host."""
+    method: str
+    moments: list
+    theta: float
+    se: float
+    sigma2: float
+    nu2: float
+    scenario: SensBounds           # the call's (cf_y, cf_d, rho, level)
+    null: float
+    rv: float
+    rva: float
+    benchmarks: list = field(default_factory=list)    # SensBenchmark per covariate set
+    diagnostics: dict = field(default_factory=dict)
+
+    @classmethod
+    def from_moments(cls, method, moments, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0,
+                     short=(), **diag):
+        """``short``: (columns, moments of the model without them) per benchmark set."""
+        mom = [float(v) for v in moments]
+        n, theta, sigma2, nu2, v11 = sens_plugins(mom)[:5]
+        rv, rva = sens_robustness(mom, rho, level, null)
+        return cls(method, mom, theta, math.sqrt(v11 / n), sigma2, nu2,
+                   sens_bounds(mom, cf_y, cf_d, rho, level), float(null), rv, rva,
+                   [sens_benchmark(cols, mom, ms) for cols, ms in short], diag)
+
+    @property
+    def ate(self):
+        return self.theta
+
+    def bounds(self, cf_y, cf_d, rho=1.0, level=0.95) -> SensBounds:
+        """The bounds and their CI under another scenario (no GPU work)."""
+        return sens_bounds(self.moments, cf_y, cf_d, rho, level)
+
+    def table(self) -> str:
+        s = self.scenario
+        lines = [f"{self.method}: theta {self.theta:.4f}, SE {self.se:.4f}, sigma2 "
+                 f"{self.sigma2:.4f}, nu2 {self.nu2:.4f}",
+                 f"{'cf_y':>9s} {'cf_d':>9s} {'rho':>9s} {'ci_lower':>9s} {'th_lower':>9s} "
+                 f"{'theta':>9s} {'th_upper':>9s} {'ci_upper':>9s}",
+                 f"{s.cf_y:9.4f} {s.cf_d:9.4f} {s.rho:9.4f} {s.ci_lower:9.4f} "
+                 f"{s.theta_lower:9.4f} {self.theta:9.4f} {s.theta_upper:9.4f} {s.ci_upper:9.4f}",
+                 f"robustness to null {self.null:g} at level {s.level:g}: RV {self.rv:.4%}, "
+                 f"RVa {self.rva:.4%}"]
+        if self.benchmarks:
+            lines.append(f"{'benchmark':>20s} {'cf_y':>9s} {'cf_d':>9s} {'rho':>9s} "
+                         f"{'d_theta':>9s} {'cf_y_raw':>10s} {'cf_d_raw':>10s}")
+            for b in self.benchmarks:
+                name = ",".join(str(c) for c in b.columns)
+                name = name if len(name) <= 20 else name[:17] + "..."
+                lines.append(f"{name:>20s} {b.cf_y:9.4f} {b.cf_d:9.4f} {b.rho:9.4f} "
+                             f"{b.delta_theta:9.4f} {b.cf_y_raw:10.3e} {b.cf_d_raw:10.3e}")
+        return "\n".join(lines)
+
+    def to_json(self):
+        keep = lambda d: {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v))
+                          for k, v in d.items()}
+        return json.dumps({"method": self.method, "theta": self.theta, "se": self.se,
+                           "sigma2": self.sigma2, "nu2": self.nu2, "null": self.null,
+                           "scenario": asdict(self.scenario), "rv": self.rv, "rva": self.rva,
+                           "benchmarks": [asdict(b) for b in self.benchmarks],
+                           "moments": self.moments, "diagnostics": keep(self.diagnostics)})
+
+
 def results_frame(results):
     import pandas as pd
     return pd.DataFrame([r.row() for r in results])

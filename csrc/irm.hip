@@ -11,7 +11,8 @@
 //   {S psi, S psi^2, n, n_clipped, S w (y - g1)^2, S (1 - w)(y - g0)^2, S (w - m)^2, n_treated}
 // are accumulated in fp64: no per-row value is written to HBM (ate_irm_score_moments), or,
 // by the same kernels instantiated with ROWS, psi_i itself is written per row for the group
-// bootstrap of csrc/gate.hip (ate_irm_scores). w is read from the panel
+// bootstrap of csrc/gate.hip (ate_irm_scores), or, instantiated with SENS, the 14 moments of
+// the sensitivity analysis are accumulated (ate_irm_sens_moments). w is read from the panel
 // on every row, never inferred from the segment. Only the columns in the union of the three
 // LASSO supports are read, once each; the coefficient triple is staged in LDS. y / w are
 // rebuilt from their hi + lo bf16 columns on bf16 panels. Structure as csrc/dml.hip.
@@ -21,7 +22,13 @@ using namespace ate;
 
 namespace {
 
-constexpr int NM = 8;   // moments
+// What a score pass produces: the 8 moments above, psi per row, or the 14 moments of the
+// sensitivity analysis (ate_irm_sens_moments below).
+enum Mode { MOMENTS = 0, ROWS = 1, SENS = 2 };
+
+constexpr int NM = 8;    // moments of MOMENTS
+constexpr int NS = 14;   // moments of SENS
+template <int MODE> constexpr int nmom() { return MODE == SENS ? NS : NM; }
 
 template <typename T>
 __device__ __forceinline__ double ld_col(const T* X, int64_t ld, int c, int64_t i) {
@@ -86,19 +93,53 @@ __device__ __forceinline__ void irm_accumulate(double (&v)[NM], double y, double
   v[7] += w;
 }
 
-__device__ __forceinline__ void write_partial(double (&v)[NM], double* red, double* partial) {
-  block_sum<NM>(v, red);
+// one valid row's contribution to the 14 moments of the sensitivity analysis, with
+//   b = (y - g_w)^2, rr = w / e - (1 - w) / (1 - e), c = 2 (1 / e + 1 / (1 - e)) - rr^2:
+//   {S psi, S psi^2, n, n_clipped, S b, S b^2, S c, S c^2, S psi b, S psi c, S b c, S y,
+//    S y^2, n_treated}
+// psi, psi^2, n, n_clipped and n_treated as irm_accumulate, term for term.
+__device__ __forceinline__ void irm_accumulate(double (&v)[NS], double y, double w, double g0,
+                                               double g1, double m, double clip) {
+  const double lo = clip, hi = 1.0 - clip;
+  const double e = m < lo ? lo : (m > hi ? hi : m);
+  const double r1 = y - g1, r0 = y - g0;
+  const double psi = irm_psi(y, w, g0, g1, m, clip);
+  const double b = w != 0.0 ? r1 * r1 : r0 * r0;
+  // two fp64 divisions beside the two of psi (the pass is bound by them, not by HBM, once
+  // there are six): for w in {0, 1}, w * (1 / e) is w / e to the bit
+  const double ie = 1.0 / e, i1e = 1.0 / (1.0 - e);
+  const double rr = w * ie - (1.0 - w) * i1e;
+  const double c = 2.0 * (ie + i1e) - rr * rr;
+  v[0] += psi;
+  v[1] += psi * psi;
+  v[2] += 1.0;
+  v[3] += (m < lo || m > hi) ? 1.0 : 0.0;
+  v[4] += b;
+  v[5] += b * b;
+  v[6] += c;
+  v[7] += c * c;
+  v[8] += psi * b;
+  v[9] += psi * c;
+  v[10] += b * c;
+  v[11] += y;
+  v[12] += y * y;
+  v[13] += w;
+}
+
+template <int N>
+__device__ __forceinline__ void write_partial(double (&v)[N], double* red, double* partial) {
+  block_sum<N>(v, red);
   if (threadIdx.x == 0) {
-    double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * NM;
+    double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * N;
 #pragma unroll
-    for (int q = 0; q < NM; ++q) out[q] = v[q];
+    for (int q = 0; q < N; ++q) out[q] = v[q];
   }
 }
 
 // fp32 / fp64 column-major panels: fp64 dot products, RPT rows per thread 256 apart.
-// ROWS: `partial` is psi[ld] instead -- every row of the segment gets its score (0 on a
-// padding row) and no moment is accumulated (ate_irm_scores).
-template <typename T, int RPT, bool ROWS>
+// MODE ROWS: `partial` is psi[ld] instead -- every row of the segment gets its score (0 on a
+// padding row) and no moment is accumulated (ate_irm_scores). SENS: the 14 moments.
+template <typename T, int RPT, int MODE>
 __global__ __launch_bounds__(256) void irm_score_kernel(
     const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p, int P,
     const Seg* __restrict__ segs, int nseg, int spf,
@@ -109,7 +150,8 @@ __global__ __launch_bounds__(256) void irm_score_kernel(
   double* c1 = sh + (p + 1);            // [p+1]
   double* cm = sh + 2 * (p + 1);        // [p+1]
   int* xc = (int*)(sh + 3 * (p + 1));   // [p]
-  __shared__ double red[16 * NM];       // static LDS: 1024 + 64 bytes (a multiple of 16)
+  constexpr int N = nmom<MODE>();
+  __shared__ double red[16 * N];        // static LDS: 1024 (SENS: 1792) + 64 bytes
   __shared__ int wcnt[16];
   const int s = blockIdx.y, k = s / spf;
   ATE_DASSERT(s < nseg && spf >= 1 && y0 >= 0 && w0 >= 0 && vcol >= 0);
@@ -127,7 +169,7 @@ __global__ __launch_bounds__(256) void irm_score_kernel(
   p = compact_support3(c0, c1, cm, xc, p, wcnt);
   const Seg sg = segs[s];
   ATE_DASSERT(sg.r0 >= 0 && sg.r0 <= sg.r1 && sg.r1 <= ld);
-  double v[NM] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double v[N] = {};
   for (int64_t base = sg.r0 + (int64_t)blockIdx.x * 256 * RPT; base < sg.r1;
        base += (int64_t)gridDim.x * 256 * RPT) {
     double a0[RPT], a1[RPT], am[RPT];
@@ -154,24 +196,24 @@ __global__ __launch_bounds__(256) void irm_score_kernel(
     for (int r = 0; r < RPT; ++r) {
       if (ii[r] >= sg.r1) continue;
       if (ld_col(X, ld, vcol, ii[r]) == 0.0) {                  // padding row
-        if (ROWS) partial[ii[r]] = 0.0;
+        if (MODE == ROWS) partial[ii[r]] = 0.0;
         continue;
       }
       const double y = ld_col(X, ld, y0, ii[r]) + (y1 >= 0 ? ld_col(X, ld, y1, ii[r]) : 0.0);
       const double w = ld_col(X, ld, w0, ii[r]) + (w1 >= 0 ? ld_col(X, ld, w1, ii[r]) : 0.0);
       ATE_DASSERT(spf != 2 || w == (double)(s & 1));
-      if (ROWS) partial[ii[r]] = irm_psi(y, w, a0[r], a1[r], am[r], clip);
+      if (MODE == ROWS) partial[ii[r]] = irm_psi(y, w, a0[r], a1[r], am[r], clip);
       else irm_accumulate(v, y, w, a0[r], a1[r], am[r], clip);
     }
   }
-  if (!ROWS) write_partial(v, red, partial);
+  if (MODE != ROWS) write_partial<N>(v, red, partial);
 }
 
 // bf16 panels: each thread owns 8 CONSECUTIVE rows, so every column read is one 16-byte
 // load through (cs, bs) (column-major and 64-row blocked panels); dot products in fp32
 // (bf16 values are exact in fp32; coefficients rounded to fp32), the score in fp64.
-// ROWS: as irm_score_kernel.
-template <bool ROWS>
+// MODE: as irm_score_kernel.
+template <int MODE>
 __global__ __launch_bounds__(256) void irm_score_bf16_kernel(
     const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
     int P, int64_t ld, const Seg* __restrict__ segs, int nseg, int spf,
@@ -182,7 +224,8 @@ __global__ __launch_bounds__(256) void irm_score_bf16_kernel(
   float* c1 = shf + (p + 1);             // [p+1]
   float* cm = shf + 2 * (p + 1);         // [p+1]
   int* xc = (int*)(shf + 3 * (p + 1));   // [p]
-  __shared__ double red[16 * NM];
+  constexpr int N = nmom<MODE>();
+  __shared__ double red[16 * N];
   __shared__ int wcnt[16];
   const int s = blockIdx.y, k = s / spf;
   ATE_DASSERT(s < nseg && spf >= 1 && y0 >= 0 && w0 >= 0 && vcol >= 0);
@@ -212,7 +255,7 @@ __global__ __launch_bounds__(256) void irm_score_bf16_kernel(
       o[2 * q + 1] = __uint_as_float(w[q] & 0xFFFF0000u);
     }
   };
-  double v[NM] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double v[N] = {};
   for (int64_t i = sg.r0 + ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < sg.r1;
        i += (int64_t)gridDim.x * 256 * 8) {
     float a0[8], a1[8], am[8];
@@ -235,49 +278,51 @@ __global__ __launch_bounds__(256) void irm_score_bf16_kernel(
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       if (vv[r] == 0.f) {                                         // padding row
-        if (ROWS) partial[i + r] = 0.0;
+        if (MODE == ROWS) partial[i + r] = 0.0;
         continue;
       }
       const double y = (double)ya[r] + (double)yb[r];
       const double w = (double)wa[r] + (double)wb[r];
       ATE_DASSERT(spf != 2 || w == (double)(s & 1));
-      if (ROWS) partial[i + r] = irm_psi(y, w, (double)a0[r], (double)a1[r], (double)am[r], clip);
+      if (MODE == ROWS) partial[i + r] = irm_psi(y, w, (double)a0[r], (double)a1[r], (double)am[r], clip);
       else irm_accumulate(v, y, w, (double)a0[r], (double)a1[r], (double)am[r], clip);
     }
   }
-  if (!ROWS) write_partial(v, red, partial);
+  if (MODE != ROWS) write_partial<N>(v, red, partial);
 }
 
 // one block of 256 threads: thread i sums partials i, i+256, ... (fixed order), then a
-// fixed-shape block reduction -> deterministic for a given launch geometry (the 8-moment
+// fixed-shape block reduction -> deterministic for a given launch geometry (the N-moment
 // sibling of csrc/dml.hip sum7_kernel)
+template <int N>
 __global__ __launch_bounds__(256) void irm_sum_kernel(const double* __restrict__ partial, int nb,
                                                       double* __restrict__ out) {
-  __shared__ double red[16 * NM];
-  double v[NM] = {0, 0, 0, 0, 0, 0, 0, 0};
+  __shared__ double red[16 * N];
+  double v[N] = {};
   for (int b = threadIdx.x; b < nb; b += 256)
 #pragma unroll
-    for (int q = 0; q < NM; ++q) v[q] += partial[(int64_t)b * NM + q];
-  block_sum<NM>(v, red);
+    for (int q = 0; q < N; ++q) v[q] += partial[(int64_t)b * N + q];
+  block_sum<N>(v, red);
   if (threadIdx.x == 0)
 #pragma unroll
-    for (int q = 0; q < NM; ++q) out[q] = v[q];
+    for (int q = 0; q < N; ++q) out[q] = v[q];
 }
 
-template <typename T, bool ROWS>
+template <typename T, int MODE>
 int irm_score_t(const void* X, int64_t ld, const void* xcols, int p, int P, const void* segs,
                 int nseg, int spf, const void* coef, int y0, int y1, int w0, int w1, int vcol,
                 double clip, int nbx, void* partial, size_t sh, hipStream_t s) {
-  ATE_LAUNCH((irm_score_kernel<T, 4, ROWS>), dim3(nbx, nseg), dim3(256), sh, s, (const T*)X, ld,
+  ATE_LAUNCH((irm_score_kernel<T, 4, MODE>), dim3(nbx, nseg), dim3(256), sh, s, (const T*)X, ld,
              (const int*)xcols, p, P, (const Seg*)segs, nseg, spf, (const double*)coef, y0, y1,
              w0, w1, vcol, clip, (double*)partial);
   ATE_CHECK_LAUNCH();
   return 0;
 }
 
-// The score pass of both entry points (argument checks and the launch): ROWS writes psi[ld]
-// through `out`, otherwise `out` is the partial buffer [nseg*nbx][8] of the moment pass.
-template <bool ROWS>
+// The score pass of every entry point (argument checks and the launch): ROWS writes psi[ld]
+// through `out`, otherwise `out` is the partial buffer [nseg*nbx][8] (SENS: [14]) of the
+// moment pass.
+template <int MODE>
 int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols, int p,
              const void* segs, int nseg, int segs_per_fold, const void* coef, int y0, int y1,
              int w0, int w1, int vcol, double clip, int nbx, void* out, hipStream_t s) {
@@ -294,12 +339,12 @@ int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols
   const size_t sh = (size_t)3 * (p + 1) * esz + (size_t)p * sizeof(int);
   if (sh > 64 * 1024 - 2048) return -1;     // dynamic + static LDS within the 64 KB default
   if (dtype == 1)
-    return irm_score_t<float, ROWS>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
+    return irm_score_t<float, MODE>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
                                     w0, w1, vcol, clip, nbx, out, sh, s);
   if (dtype == 2)
-    return irm_score_t<double, ROWS>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
+    return irm_score_t<double, MODE>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
                                      w0, w1, vcol, clip, nbx, out, sh, s);
-  ATE_LAUNCH(irm_score_bf16_kernel<ROWS>, dim3(nbx, nseg), dim3(256), sh, s, (const bf16_t*)X, cs,
+  ATE_LAUNCH(irm_score_bf16_kernel<MODE>, dim3(nbx, nseg), dim3(256), sh, s, (const bf16_t*)X, cs,
              bs, (const int*)xcols, p, P, ld, (const Seg*)segs, nseg, segs_per_fold,
              (const double*)coef, y0, y1, w0, w1, vcol, clip, (double*)out);
   ATE_CHECK_LAUNCH();
@@ -318,10 +363,10 @@ ATE_API int ate_irm_score_moments(int dtype, const void* X, int64_t cs, int64_t 
                                   int w1, int vcol, double clip, int nbx, void* partial,
                                   void* moments, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int rc = irm_pass<false>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0,
+  const int rc = irm_pass<MOMENTS>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0,
                                  y1, w0, w1, vcol, clip, nbx, partial, s);
   if (rc != 0) return rc;
-  ATE_LAUNCH(irm_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
+  ATE_LAUNCH(irm_sum_kernel<NM>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
              (double*)moments);
   ATE_CHECK_LAUNCH();
   return 0;
@@ -334,6 +379,26 @@ ATE_API int ate_irm_scores(int dtype, const void* X, int64_t cs, int64_t bs, con
                            int p, const void* segs, int nseg, int segs_per_fold,
                            const void* coef, int y0, int y1, int w0, int w1, int vcol,
                            double clip, int nbx, void* psi, void* stream) {
-  return irm_pass<true>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0, y1, w0,
+  return irm_pass<ROWS>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0, y1, w0,
                         w1, vcol, clip, nbx, psi, (hipStream_t)stream);
+}
+
+// The pass of ate_irm_score_moments -- same arguments and checks, same column reads, dot
+// products and psi -- accumulating the 14 moments of the sensitivity analysis (irm_accumulate
+// above). partial: [nseg*nbx][14]; moments: [14]. For the same nbx, moments 0-3 and 13 carry
+// the bits of moments 0-3 and 7 of ate_irm_score_moments (same per-thread order, same
+// reduction shape).
+ATE_API int ate_irm_sens_moments(int dtype, const void* X, int64_t cs, int64_t bs,
+                                 const void* xcols, int p, const void* segs, int nseg,
+                                 int segs_per_fold, const void* coef, int y0, int y1, int w0,
+                                 int w1, int vcol, double clip, int nbx, void* partial,
+                                 void* moments, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = irm_pass<SENS>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0,
+                                y1, w0, w1, vcol, clip, nbx, partial, s);
+  if (rc != 0) return rc;
+  ATE_LAUNCH(irm_sum_kernel<NS>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
+             (double*)moments);
+  ATE_CHECK_LAUNCH();
+  return 0;
 }
