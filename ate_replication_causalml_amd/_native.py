@@ -103,6 +103,10 @@ _SIGS = {
     "ate_irm_sens_moments": "ipllpipiipiiiiidippp",
     "ate_group_boot": "pppliiuippp",
     "ate_group_boot_scratch": "iii",
+    "ate_cate_moments": "ppplpiiippp",
+    "ate_cate_moments_scratch": "iii",
+    "ate_cate_boot": "ppplppiiiuippp",
+    "ate_cate_boot_scratch": "iiii",
     "ate_lognet_path": "iplpiipipipdddippippppppppp",
     "ate_lognet_cvloss": "iplpiippipppipp",
     "ate_dgp_fill": "iplllllp" + "uiipppp",
@@ -145,7 +149,9 @@ _SIGS = {
 _RESTYPE = {"ate_forest_scratch_bytes": ctypes.c_int64,
             "ate_forest_exact_scratch_bytes": ctypes.c_int64, "ate_gbdt_slab_entries": ctypes.c_int64,
             "ate_gbdt_slab2_entries": ctypes.c_int64,
-            "ate_scan_parts": ctypes.c_int64, "ate_group_boot_scratch": ctypes.c_int64}
+            "ate_scan_parts": ctypes.c_int64, "ate_group_boot_scratch": ctypes.c_int64,
+            "ate_cate_moments_scratch": ctypes.c_int64,
+            "ate_cate_boot_scratch": ctypes.c_int64}
 _CT = {"p": c_void_p, "i": c_int, "l": c_int64, "u": c_uint64, "d": c_double}
 
 

@@ -19,6 +19,8 @@ ate_double_ml; residual_balance_ATE -> ate_residual_balance; grf::causal_forest 
 estimate_average_effect -> ate_causal_forest; K-fold DML-PLR -> ate_dml; K-fold DML-IRM
 (cross-fitted AIPW, LASSO nuisances) -> ate_dml_irm; its group effects with a joint
 multiplier-bootstrap band (DoubleML gate / bootstrap / confint(joint=True)) -> ate_dml_irm_gate;
+its effect curve along one covariate on a B-spline basis with a uniform band (DoubleML
+cate(basis) / confint(joint=True)) -> ate_dml_irm_cate;
 its sensitivity to unobserved confounding (DoubleML sensitivity_analysis /
 sensitivity_benchmark) -> ate_dml_irm_sensitivity.
 """
@@ -30,7 +32,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import AteResult, GateResult, SensitivityResult, format_table, results_frame
+from .result import AteResult, CateResult, GateResult, SensitivityResult, format_table, results_frame
 from .utils import guards
 from .utils.tracing import trace
 
@@ -271,6 +273,30 @@ def ate_dml_irm_gate(Y, W, X, groups, folds=5, lambda_rule="min", clip=0.01, n_b
                                      dtype=run.dtype)
 
 
+def ate_dml_irm_cate(Y, W, X, by, df=5, degree=3, knots=None, grid=None, folds=5,
+                     lambda_rule="min", clip=0.01, n_boot=999, level=0.95,
+                     method="DML-IRM CATE curve (LASSO)", run=None) -> CateResult:
+    """The conditional average treatment effect of ate_dml_irm along one covariate ``by`` (a
+    column index into X, or an (n,) vector): the projection of the AIPW score on a B-spline
+    basis (``df`` <= 32 functions of ``degree`` 0..3, quantile knots unless ``knots`` is
+    given) evaluated on ``grid`` (default: 100 points between the 5 % and 95 % order
+    statistics), with pointwise and uniform ``level`` confidence bounds, the latter from
+    ``n_boot`` Rademacher multiplier-bootstrap draws of the maximal t-statistic over the grid
+    (estimators/cate.py). Further points: ``result.predict(x)``."""
+    run = _run(run)
+    with trace("ate_dml_irm_cate", folds=folds, n_boot=n_boot):
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_irm_cate(Y, W, X, by, df=df, degree=degree, knots=knots, grid=grid,
+                                  n_boot=n_boot, level=level, folds=folds, seed=run.seed,
+                                  lambda_rule=lambda_rule, clip=clip, method=method)
+        from .estimators import cate as DC
+        return DC.dml_irm_cate_lasso(Y, W, X, by, df=df, degree=degree, knots=knots, grid=grid,
+                                     n_boot=n_boot, level=level, folds=folds, seed=run.seed,
+                                     lambda_rule=lambda_rule, clip=clip, method=method,
+                                     device=run.device(), dtype=run.dtype)
+
+
 def ate_dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0,
                             benchmarks=None, folds=5, lambda_rule="min", clip=0.01,
                             run=None) -> SensitivityResult:
@@ -466,7 +492,7 @@ def replicate(data=None, config: ReplicateConfig | None = None, log_path=None, p
 __all__ = [
     "ate_naive", "ate_ols", "propensity_logistic", "propensity_lasso", "ate_ipw", "ate_ipw_wls",
     "ate_lasso_single", "ate_lasso", "ate_aipw_rf", "ate_aipw_glm", "ate_belloni",
-    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_sensitivity", "ate_residual_balance", "ate_causal_forest", "replicate",
+    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_sensitivity", "ate_residual_balance", "ate_causal_forest", "replicate",
     "ate_aipw_crossfit", "ate_causal_forest_bootstrap",
-    "Replication", "AteResult", "GateResult", "SensitivityResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
+    "Replication", "AteResult", "CateResult", "GateResult", "SensitivityResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
 ]

@@ -50,6 +50,34 @@ def _dml(a):
                               arm_split=True)
         if a.gate_col is not None and a.sensitivity:
             raise SystemExit("--gate-col and --sensitivity are separate analyses: pick one")
+        if a.cate_col is not None and (a.gate_col is not None or a.sensitivity):
+            raise SystemExit("--cate-col, --gate-col and --sensitivity are separate analyses: "
+                             "pick one")
+        if a.cate_col is not None:
+            # the effect curve along covariate x{cate_col} on a B-spline basis, uniform band
+            import numpy as np
+            from .estimators import cate as DC
+            from .result import AteResult, CateResult
+            if not 1 <= a.cate_grid <= DC.GRID_MAX:
+                raise SystemExit(f"--cate-grid must be in [1, {DC.GRID_MAX}]")
+            knots = DC.spline_knots(pan, a.cate_col, a.cate_df, a.cate_degree)
+            x = pan.col(f"x{a.cate_col}").double()
+            xs = torch.sort(x[pan.row_index >= 0]).values
+            n = xs.numel()
+            grid = np.linspace(float(xs[(5 * n) // 100]), float(xs[min((95 * n) // 100, n - 1)]),
+                               a.cate_grid)
+            fin, _, _, _ = DC.irm_cate_panel(pan, x, knots, a.cate_degree, grid, a.folds,
+                                             a.lambda_rule, a.clip, n_boot=a.boot, seed=a.seed)
+            cate, se, crit, o_ate, o_se, nn, beta, omega = DC.read_fin(
+                fin.double().cpu().numpy(), a.cate_df, a.cate_grid)
+            r = CateResult.make("DML-IRM CATE curve (LASSO)", grid, cate, se, crit, beta, omega,
+                                knots.cpu().numpy(), a.cate_degree, a.boot, 0.95,
+                                AteResult.make("DML-IRM cross-fit (LASSO)", o_ate, o_se, n=a.n))
+            out = {"curve": r.rows(), "crit": r.crit, "n_boot": r.n_boot, "level": r.level,
+                   "knots": r.knots, "degree": r.degree, "coef": r.coef, "n": int(round(nn)),
+                   "ate": r.overall.ate, "se": r.overall.se}
+            print(json.dumps(out))
+            return 0
         if a.gate_col is not None:
             # group effects over quantile bins of covariate x{gate_col}, with a joint band
             from .estimators.gate import irm_gate_panel, quantile_groups
@@ -157,7 +185,13 @@ def main(argv=None):
                    help="irm: group ATEs over quantile bins of covariate x{J}, with a joint band")
     d.add_argument("--gate-bins", type=int, default=4, help="irm --gate-col: quantile groups")
     d.add_argument("--boot", type=int, default=999,
-                   help="irm --gate-col: multiplier-bootstrap draws of the joint band")
+                   help="irm --gate-col / --cate-col: multiplier-bootstrap draws of the joint band")
+    d.add_argument("--cate-col", type=int, default=None,
+                   help="irm: the effect curve along covariate x{J} (B-splines), uniform band")
+    d.add_argument("--cate-df", type=int, default=5, help="irm --cate-col: basis functions")
+    d.add_argument("--cate-degree", type=int, default=3, help="irm --cate-col: spline degree 0..3")
+    d.add_argument("--cate-grid", type=int, default=100,
+                   help="irm --cate-col: points of the curve, between the 5 %% and 95 %% quantiles")
     d.add_argument("--sensitivity", action="store_true",
                    help="irm: bounds under unobserved confounding, robustness values")
     d.add_argument("--cf-y", type=float, default=0.03, help="irm --sensitivity: outcome strength")

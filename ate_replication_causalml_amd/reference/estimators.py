@@ -461,6 +461,136 @@ def dml_irm_gate(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", clip=0.
     return res
 
 
+def bspline_design(x, knots, degree):
+    """The B-spline design matrix [n, df] of the points x on a clamped knot vector, point by
+    point from the textbook recursive Cox-de Boor definition (result.bspline_row)."""
+    from ..result import bspline_row
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    d = len(knots) - int(degree) - 1
+    return np.array([bspline_row(v, knots, degree) for v in x]).reshape(len(x), d)
+
+
+def _check_cate_basis(df, degree):
+    if int(degree) != degree or not 0 <= int(degree) <= 3:
+        raise ValueError(f"degree must be an integer in 0..3, got {degree}")
+    if int(df) != df or not int(degree) + 1 <= int(df) <= 32:
+        raise ValueError(f"df must be an integer in [degree + 1, 32] = [{int(degree) + 1}, 32], "
+                         f"got {df}")
+
+
+def _check_cate_knots(knots, degree):
+    t = np.asarray(knots, dtype=np.float64).reshape(-1)
+    _check_cate_basis(len(t) - degree - 1, degree)
+    q = int(degree)
+    d = len(t) - q - 1
+    if not np.isfinite(t).all() or np.any(t[:q + 1] != t[0]) or np.any(t[d:] != t[-1]):
+        raise ValueError("the knot vector must be finite and clamped: the boundary knots "
+                         f"repeated degree + 1 = {q + 1} times")
+    if not np.all(np.diff(t[q:d + 1]) > 0):
+        raise ValueError("the knots are not strictly increasing (too few distinct values of "
+                         f"the covariate for df = {d}, degree = {q}?): {t[q:d + 1].tolist()}")
+    return t
+
+
+def cate_from_scores(psi, x, knots, degree, grid, n_boot=999, level=0.95, seed=1991,
+                     row_ids=None):
+    """The projection of per-row scores on a B-spline basis of x with the multiplier-bootstrap
+    critical value of the curve's uniform band, in float64 (the twin of estimators/cate.py):
+    beta = (S b b')^-1 S b psi, the HC0 covariance Omega = M^-1 (S e^2 b b') M^-1 with
+    e = psi - b' beta, cate = g' beta and se = sqrt(g' Omega g) at the grid's basis rows g,
+    and with Rademacher multipliers xi (rng.rademacher, keyed by ``row_ids``, default 0..n-1)
+    t[b, j] = g_j' M^-1 S xi^b e b / se_j, crit = the ceil(level n_boot)-th smallest of
+    max_j |t[b, .]|. Returns a dict: cate, se, crit, beta, cov, M, meat, T [B, df],
+    span_counts."""
+    from ..result import boot_rank
+    psi = np.asarray(psi, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    t = np.asarray(knots, dtype=np.float64)
+    q, B = int(degree), int(n_boot)
+    d = len(t) - q - 1
+    Bm = bspline_design(x, t, q)
+    G = bspline_design(grid, t, q)
+    rows = np.arange(len(psi)) if row_ids is None else np.asarray(row_ids)
+    M = Bm.T @ Bm
+    beta = np.linalg.solve(M, Bm.T @ psi)
+    EB = Bm * (psi - Bm @ beta)[:, None]
+    meat = EB.T @ EB
+    Minv = np.linalg.inv(M)
+    cov = Minv @ meat @ Minv
+    cate = G @ beta
+    se = np.sqrt(np.einsum("jk,kl,jl->j", G, cov, G))
+    T = np.zeros((B, d))
+    for i0 in range(0, len(psi), 8192):
+        sl = slice(i0, i0 + 8192)
+        T += rng.rademacher(seed, rows[sl], B).T.astype(np.float64) @ EB[sl]
+    tstat = (T @ Minv @ G.T) / se
+    crit = np.sort(np.abs(tstat).max(axis=1))[boot_rank(level, B) - 1]
+    span = np.searchsorted(t[q + 1:d], x, side="right")
+    return dict(cate=cate, se=se, crit=float(crit), beta=beta, cov=cov, M=M, meat=meat, T=T,
+                span_counts=np.bincount(span, minlength=d - q))
+
+
+def dml_irm_cate(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boot=999, level=0.95,
+                 folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                 method="DML-IRM CATE curve (LASSO)", fold_ids=None, keep_boot=False):
+    """The CATE curve of the cross-fitted interactive model along one covariate with a uniform
+    confidence band (the float64 twin of estimators.cate.dml_irm_cate_lasso): the scores of
+    dml_irm_lasso projected on a B-spline basis of ``by`` (a column index into X, or an (n,)
+    vector) by cate_from_scores. Default knots: the order statistics at rank k n / (df -
+    degree) between min and max; default grid: 100 equally spaced points between the 5 % and
+    95 % order statistics."""
+    from ..result import CateResult, boot_rank
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    if int(n_boot) != n_boot or not 1 <= int(n_boot) <= 4096:
+        raise ValueError(f"n_boot must be an integer in [1, 4096], got {n_boot}")
+    boot_rank(level, int(n_boot))
+    if np.ndim(by) == 0:
+        if int(by) != by or not 0 <= int(by) < X.shape[1]:
+            raise ValueError(f"by must index the {X.shape[1]} columns of X, got {by}")
+        x = X[:, int(by)].copy()
+    else:
+        x = _arr(by).reshape(-1)
+        if len(x) != len(Y):
+            raise ValueError(f"by must be a vector with one value per row ({len(Y)}), "
+                             f"got shape {np.shape(by)}")
+    xs = np.sort(x)
+    n = len(x)
+    if knots is None:
+        _check_cate_basis(df, degree)
+        q = int(degree)
+        bins = int(df) - q
+        inner = xs[[(k * n) // bins for k in range(1, bins)]]
+        knots = np.concatenate([[xs[0]] * (q + 1), inner, [xs[-1]] * (q + 1)])
+    t = _check_cate_knots(knots, degree)
+    q = int(degree)
+    d = len(t) - q - 1
+    if xs[0] < t[0] or xs[-1] > t[-1]:
+        raise ValueError(f"the boundary knots [{t[0]}, {t[-1]}] must contain every x "
+                         f"([{xs[0]}, {xs[-1]}])")
+    if grid is None:
+        grid = np.linspace(xs[(5 * n) // 100], xs[min((95 * n) // 100, n - 1)], 100)
+    grid = np.asarray(grid, dtype=np.float64).reshape(-1)
+    if not 1 <= len(grid) <= 512:
+        raise ValueError(f"the grid must have between 1 and 512 points, got {len(grid)}")
+    if not (np.isfinite(grid).all() and grid.min() >= t[0] and grid.max() <= t[-1]):
+        raise ValueError(f"grid points must lie inside [min x, max x] = [{t[0]}, {t[-1]}]")
+    for s, c in enumerate(np.bincount(np.searchsorted(t[q + 1:d], x, side="right"),
+                                      minlength=d - q)):
+        if c < 2:
+            raise ValueError(f"span {s} of the knot vector has {int(c)} row(s): every span "
+                             "needs at least 2")
+    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    r = cate_from_scores(psi, x, t, q, grid, n_boot, level, seed)
+    overall = AteResult.make("DML-IRM cross-fit (LASSO)", psi.mean(),
+                             psi.std(ddof=1) / np.sqrt(n), n=n)
+    res = CateResult.make(method, grid, r["cate"], r["se"], r["crit"], r["beta"], r["cov"], t, q,
+                          int(n_boot), level, overall,
+                          span_counts=[int(c) for c in r["span_counts"]])
+    if keep_boot:
+        res.boot = {"T": r["T"], "M": r["M"], "meat": r["meat"]}
+    return res
+
+
 def sensitivity_from_rows(psi, b, c, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0):
     """The sensitivity figures of per-row (psi, b, c), row by row in float64 -- written
     independently of the moment route of result.SensitivityResult: the SEs are

@@ -109,6 +109,113 @@ class GateResult:
                            "diagnostics": keep(self.diagnostics)}, default=str)
 
 
+def bspline_row(x: float, knots, degree: int) -> list:
+    """The B-spline basis values [df] at one point of a clamped knot vector, by the textbook
+    recursive Cox-de Boor definition (0 / 0 := 0; spans half-open, the last one closed on
+    the right) -- float64 on the host, an algorithm of its own beside the kernels'
+    span-local recurrence."""
+    t = [float(v) for v in knots]
+    q = int(degree)
+    d = len(t) - q - 1
+    x = float(x)
+
+    def b(j, k):
+        if k == 0:
+            if t[j] <= x < t[j + 1]:
+                return 1.0
+            # the last non-empty span is closed on the right
+            return 1.0 if (x == t[-1] and t[j] < t[j + 1] == t[-1]) else 0.0
+        out = 0.0
+        if t[j + k] > t[j]:
+            out += (x - t[j]) / (t[j + k] - t[j]) * b(j, k - 1)
+        if t[j + k + 1] > t[j + 1]:
+            out += (t[j + k + 1] - x) / (t[j + k + 1] - t[j + 1]) * b(j + 1, k - 1)
+        return out
+
+    return [b(j, q) for j in range(d)]
+
+
+@dataclass
+class CateResult:
+    """The conditional average treatment effect along one covariate as a B-spline curve on
+    ``grid``, with pointwise and uniform (multiplier bootstrap) confidence bounds; ``coef``
+    and ``cov`` are the projection's coefficients and their HC0 covariance, ``overall`` the
+    ATE over the same rows."""
+    method: str
+    grid: list
+    cate: list
+    se: list
+    lower_ci: list                 # pointwise: cate -/+ Z se
+    upper_ci: list
+    lower_joint: list              # uniform over the grid: cate -/+ crit se
+    upper_joint: list
+    crit: float
+    coef: list                     # beta [df]
+    cov: list                      # Omega [df][df]
+    knots: list                    # clamped knot vector [df + degree + 1]
+    degree: int
+    n_boot: int
+    level: float
+    overall: AteResult
+    diagnostics: dict = field(default_factory=dict)
+    boot: dict | None = None       # keep_boot: "T" [n_boot, df], "M", "meat" [df, df]
+
+    @classmethod
+    def make(cls, method, grid, cate, se, crit, coef, cov, knots, degree, n_boot, level, overall,
+             **diag):
+        grid = [float(v) for v in grid]
+        cate = [float(v) for v in cate]
+        se = [float(v) for v in se]
+        crit = float(crit)
+        return cls(method, grid, cate, se,
+                   [a - Z * s for a, s in zip(cate, se)], [a + Z * s for a, s in zip(cate, se)],
+                   [a - crit * s for a, s in zip(cate, se)],
+                   [a + crit * s for a, s in zip(cate, se)], crit, [float(v) for v in coef],
+                   [[float(v) for v in row] for row in cov], [float(v) for v in knots],
+                   int(degree), int(n_boot), float(level), overall, diag)
+
+    @property
+    def df(self) -> int:
+        return len(self.coef)
+
+    def predict(self, x):
+        """(cate, se) at new points inside [min x, max x], on the host (no GPU work)."""
+        import numpy as np
+        pts = np.asarray(x, dtype=np.float64).reshape(-1)
+        if len(pts) and (pts.min() < self.knots[0] or pts.max() > self.knots[-1]):
+            raise ValueError(f"points must lie inside [{self.knots[0]}, {self.knots[-1]}]")
+        G = np.array([bspline_row(v, self.knots, self.degree) for v in pts]).reshape(len(pts), self.df)
+        cov = np.asarray(self.cov)
+        return G @ np.asarray(self.coef), np.sqrt(np.maximum(((G @ cov) * G).sum(axis=1), 0.0))
+
+    def rows(self):
+        return [{"x": self.grid[j], "CATE": self.cate[j], "se": self.se[j],
+                 "lower_ci": self.lower_ci[j], "upper_ci": self.upper_ci[j],
+                 "lower_joint": self.lower_joint[j], "upper_joint": self.upper_joint[j]}
+                for j in range(len(self.grid))]
+
+    def table(self) -> str:
+        lines = [f"{self.method}: df {self.df}, degree {self.degree}, uniform {self.level:.0%} "
+                 f"band, crit {self.crit:.4f} ({self.n_boot} multiplier draws)",
+                 f"{'x':>12s} {'CATE':>9s} {'SE':>9s} {'lower_ci':>9s} {'upper_ci':>9s} "
+                 f"{'lower_jt':>9s} {'upper_jt':>9s}"]
+        for r in self.rows():
+            lines.append(f"{r['x']:12.4f} {r['CATE']:9.4f} {r['se']:9.4f} {r['lower_ci']:9.4f} "
+                         f"{r['upper_ci']:9.4f} {r['lower_joint']:9.4f} {r['upper_joint']:9.4f}")
+        o = self.overall
+        lines.append(f"{'all':>12s} {o.ate:9.4f} {o.se:9.4f} {o.lower_ci:9.4f} {o.upper_ci:9.4f}")
+        return "\n".join(lines)
+
+    def to_json(self):
+        keep = lambda d: {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v))
+                          for k, v in d.items()}
+        return json.dumps({"method": self.method, "curve": self.rows(), "crit": self.crit,
+                           "coef": self.coef, "cov": self.cov, "knots": self.knots,
+                           "degree": self.degree, "n_boot": self.n_boot, "level": self.level,
+                           "overall": json.loads(self.overall.to_json()),
+                           "diagnostics": keep(self.diagnostics)}, default=str)
+
+
 # ------------------------------------------------------------ sensitivity to confounding
 # the 14 moments of the sensitivity pass (estimators/sensitivity.py, csrc/irm.hip), with
 # b = (y - g_w)^2, rr = w / e - (1 - w) / (1 - e), c = 2 (1 / e + 1 / (1 - e)) - rr^2
