@@ -21,6 +21,8 @@ estimate_average_effect -> ate_causal_forest; K-fold DML-PLR -> ate_dml; K-fold 
 multiplier-bootstrap band (DoubleML gate / bootstrap / confint(joint=True)) -> ate_dml_irm_gate;
 its effect curve along one covariate on a B-spline basis with a uniform band (DoubleML
 cate(basis) / confint(joint=True)) -> ate_dml_irm_cate;
+the exact depth-2 policy tree on its scores (DoubleML policy_tree, searched exactly as
+policytree does) -> ate_dml_irm_policy;
 its sensitivity to unobserved confounding (DoubleML sensitivity_analysis /
 sensitivity_benchmark) -> ate_dml_irm_sensitivity.
 """
@@ -32,7 +34,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import AteResult, CateResult, GateResult, SensitivityResult, format_table, results_frame
+from .result import AteResult, CateResult, GateResult, PolicyTreeResult, SensitivityResult, format_table, results_frame
 from .utils import guards
 from .utils.tracing import trace
 
@@ -297,6 +299,27 @@ def ate_dml_irm_cate(Y, W, X, by, df=5, degree=3, knots=None, grid=None, folds=5
                                      device=run.device(), dtype=run.dtype)
 
 
+def ate_dml_irm_policy(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.0, train=None,
+                       folds=5, lambda_rule="min", clip=0.01,
+                       method="DML-IRM policy tree (LASSO)", run=None) -> PolicyTreeResult:
+    """Whom to treat: the exact policy tree of depth <= 2 on the AIPW scores of ate_dml_irm
+    less ``cost``, over the columns ``features`` of X (1..32) binned into at most ``bins``
+    (2..64) bins, every split keeping ``min_leaf`` training rows on each side
+    (estimators/policy.py). ``train``: a boolean mask of the rows the tree is learned on; the
+    others give the held-out value. Without it only the in-sample value is reported, which is
+    optimistic (``diagnostics["honest"]`` is False). New rows: ``result.predict(X)``."""
+    run = _run(run)
+    with trace("ate_dml_irm_policy", folds=folds, depth=depth):
+        kw = dict(depth=depth, bins=bins, min_leaf=min_leaf, cost=cost, train=train, folds=folds,
+                  seed=run.seed, lambda_rule=lambda_rule, clip=clip, method=method)
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_irm_policy_tree(Y, W, X, features, **kw)
+        from .estimators import policy as DP
+        return DP.dml_irm_policy_lasso(Y, W, X, features, device=run.device(), dtype=run.dtype,
+                                       **kw)
+
+
 def ate_dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0,
                             benchmarks=None, folds=5, lambda_rule="min", clip=0.01,
                             run=None) -> SensitivityResult:
@@ -492,7 +515,7 @@ def replicate(data=None, config: ReplicateConfig | None = None, log_path=None, p
 __all__ = [
     "ate_naive", "ate_ols", "propensity_logistic", "propensity_lasso", "ate_ipw", "ate_ipw_wls",
     "ate_lasso_single", "ate_lasso", "ate_aipw_rf", "ate_aipw_glm", "ate_belloni",
-    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_sensitivity", "ate_residual_balance", "ate_causal_forest", "replicate",
+    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_policy", "ate_dml_irm_sensitivity", "ate_residual_balance", "ate_causal_forest", "replicate",
     "ate_aipw_crossfit", "ate_causal_forest_bootstrap",
-    "Replication", "AteResult", "CateResult", "GateResult", "SensitivityResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
+    "Replication", "AteResult", "CateResult", "GateResult", "PolicyTreeResult", "SensitivityResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
 ]

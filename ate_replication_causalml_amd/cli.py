@@ -53,6 +53,41 @@ def _dml(a):
         if a.cate_col is not None and (a.gate_col is not None or a.sensitivity):
             raise SystemExit("--cate-col, --gate-col and --sensitivity are separate analyses: "
                              "pick one")
+        if a.policy_cols is not None:
+            # whom to treat: the exact policy tree over the covariates x{J}, ...
+            if a.cate_col is not None or a.gate_col is not None or a.sensitivity:
+                raise SystemExit("--policy-cols, --cate-col, --gate-col and --sensitivity are "
+                                 "separate analyses: pick one")
+            from .estimators import policy as DP
+            from .result import PolicyTreeResult
+            try:
+                cols = [int(c) for c in a.policy_cols.split(",")]
+            except ValueError:
+                raise SystemExit("--policy-cols takes comma-separated column indices")
+            try:
+                cols = DP.check_features(cols, a.p)
+                DP.check_tree_args(a.policy_depth, a.policy_bins, 1)
+            except ValueError as e:
+                raise SystemExit(str(e))
+            real = pan.row_index >= 0
+            xs = [pan.col(f"x{j}").double() for j in cols]
+            edges = [DP.feature_edges(x[real].cpu().numpy(), a.policy_bins) for x in xs]
+            codes = torch.stack([torch.bucketize(x, torch.as_tensor(ed, device=x.device),
+                                                 right=True).to(torch.uint8)
+                                 for x, ed in zip(xs, edges)])
+            use = torch.where(real, 0, -1).to(torch.int8)
+            fin, rec, e, _ = DP.irm_policy_panel(pan, codes, use, [len(ed) + 1 for ed in edges],
+                                                 a.policy_cost, a.folds, a.policy_depth, 1,
+                                                 a.lambda_rule, a.clip, n_rows=a.n)
+            r = PolicyTreeResult.make("DML-IRM policy tree (LASSO)", rec.cpu().numpy(),
+                                      fin.double().cpu().numpy(), cols, edges, a.policy_cost,
+                                      a.policy_depth, e=int(e.item()))
+            ev = r.in_sample
+            out = {"nodes": r.nodes, "actions": r.actions, "leaves": ev["leaves"],
+                   **{k: v for k, v in ev.items() if k != "leaves"}, "honest": False,
+                   "depth": r.depth, "cost": r.cost, "features": r.features, "edges": r.edges}
+            print(json.dumps(out))
+            return 0
         if a.cate_col is not None:
             # the effect curve along covariate x{cate_col} on a B-spline basis, uniform band
             import numpy as np
@@ -192,6 +227,13 @@ def main(argv=None):
     d.add_argument("--cate-degree", type=int, default=3, help="irm --cate-col: spline degree 0..3")
     d.add_argument("--cate-grid", type=int, default=100,
                    help="irm --cate-col: points of the curve, between the 5 %% and 95 %% quantiles")
+    d.add_argument("--policy-cols", default=None, metavar="J,J,...",
+                   help="irm: the exact policy tree (whom to treat) over the covariates x{J}, ...")
+    d.add_argument("--policy-depth", type=int, default=2, help="irm --policy-cols: depth 0..2")
+    d.add_argument("--policy-bins", type=int, default=32,
+                   help="irm --policy-cols: bins per covariate, 2..64")
+    d.add_argument("--policy-cost", type=float, default=0.0,
+                   help="irm --policy-cols: the cost of treating one row, taken off every score")
     d.add_argument("--sensitivity", action="store_true",
                    help="irm: bounds under unobserved confounding, robustness values")
     d.add_argument("--cf-y", type=float, default=0.03, help="irm --sensitivity: outcome strength")

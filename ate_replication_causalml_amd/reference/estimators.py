@@ -591,6 +591,132 @@ def dml_irm_cate(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boot=999,
     return res
 
 
+def policy_tree_from_scores(r, Xf, edges, train=None, depth=2, min_leaf=1):
+    """The exact policy tree of depth <= 2 on per-row scores r over the feature columns Xf
+    (n, d) with split points ``edges`` (per feature, ascending), by brute force over row
+    masks -- written from the definitions of estimators/policy.py, sharing no code with its
+    histogram / prefix-sum search. The scores are quantised to integers q = rint(r 2^e)
+    (e = min(30, 61 - bit_length(n) - x), max|r| = m 2^x), a leaf with sum S is worth
+    max(S, 0) and treats iff S > 0, a node takes the best of staying a leaf and every split
+    (j, t) (x_j < edges[j][t] goes left) that keeps ``min_leaf`` training rows on each side;
+    the first best candidate in the order leaf, (j, t) ascending wins.
+    Returns (rec [16] ints as the kernels' tree record, fin [2][20] as policy_finalize, e)."""
+    import math
+    r = np.asarray(r, dtype=np.float64)
+    Xf = np.asarray(Xf, dtype=np.float64).reshape(len(r), -1)
+    n, d = Xf.shape
+    tr = np.ones(n, dtype=bool) if train is None else np.asarray(train, dtype=bool)
+    ok = np.isfinite(r)
+    e = min(30, 61 - n.bit_length() - math.frexp(np.abs(r[ok]).max() if ok.any() else 0.0)[1])
+    q = np.rint(np.ldexp(np.where(ok, r, 0.0), e)).astype(np.int64)
+    goes_left = {(j, t): Xf[:, j] < edges[j][t] for j in range(d) for t in range(len(edges[j]))}
+
+    def best(rows, k):
+        S = int(q[rows].sum())
+        value, tree = max(S, 0), {"split": None, "action": int(S > 0)}
+        if k == 0:
+            return value, tree
+        for (j, t), lt in goes_left.items():          # insertion order: (j, t) ascending
+            lo, hi = rows & lt, rows & ~lt
+            if lo.sum() < min_leaf or hi.sum() < min_leaf:
+                continue
+            vl, tl = best(lo, k - 1)
+            vh, th = best(hi, k - 1)
+            if vl + vh > value:
+                value, tree = vl + vh, {"split": (j, t), "lo": tl, "hi": th}
+        return value, tree
+
+    value, tree = best(tr, int(depth))
+    rec = [-1] * 6 + [0] * 4 + [value, int(tr.sum()), 0, 0, 0, 0]
+    pi = np.zeros(n, dtype=np.int64)
+    slot = np.zeros(n, dtype=np.int64)
+    if tree["split"] is None:
+        rec[6:10] = [tree["action"]] * 4
+        pi[:] = tree["action"]
+    else:
+        rec[0:2] = tree["split"]
+        right = ~goes_left[tree["split"]]
+        for side, sub in enumerate((tree["lo"], tree["hi"])):
+            here = right == bool(side)
+            if sub["split"] is None:
+                rec[6 + 2 * side:8 + 2 * side] = [sub["action"]] * 2
+                pi[here] = sub["action"]
+                slot[here] = 2 * side
+            else:
+                rec[2 + 2 * side:4 + 2 * side] = sub["split"]
+                up = ~goes_left[sub["split"]]
+                for cs, leaf in enumerate((sub["lo"], sub["hi"])):
+                    rec[6 + 2 * side + cs] = leaf["action"]
+                    pi[here & (up == bool(cs))] = leaf["action"]
+                    slot[here & (up == bool(cs))] = 2 * side + cs
+
+    def mean_se(v):
+        if len(v) == 0:
+            return [np.nan, np.nan]
+        return [v.mean(), v.std(ddof=1) / np.sqrt(len(v)) if len(v) > 1 else np.nan]
+
+    fin = []
+    for rows in (tr, ~tr):
+        rr, pp = r[rows], pi[rows]
+        row = mean_se(pp * rr) + mean_se(rr) + mean_se((pp - 1) * rr)
+        row += [pp.mean() if len(pp) else np.nan, float(len(rr))]
+        for s in range(4):
+            v = rr[slot[rows] == s]
+            row += [float(len(v))] + mean_se(v)
+        fin.append(row)
+    fin = np.asarray(fin, dtype=np.float64)
+    if not ok.all():
+        fin[:] = np.nan
+    return rec, fin, e
+
+
+def dml_irm_policy_tree(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.0, train=None,
+                        folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                        method="DML-IRM policy tree (LASSO)", fold_ids=None):
+    """The exact policy tree on the AIPW scores of the cross-fitted interactive model (the
+    float64 twin of estimators.policy.dml_irm_policy_lasso): the scores of dml_irm_lasso less
+    ``cost``, the columns ``features`` of X cut at every distinct value but the smallest (at
+    most ``bins`` distinct values) or at the order statistics of rank k n / bins, and the
+    brute-force search of policy_tree_from_scores."""
+    from ..result import PolicyTreeResult
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    if depth not in (0, 1, 2):
+        raise ValueError(f"depth must be 0, 1 or 2, got {depth}")
+    if int(bins) != bins or not 2 <= int(bins) <= 64:
+        raise ValueError(f"bins must be an integer in [2, 64], got {bins}")
+    if int(min_leaf) != min_leaf or int(min_leaf) < 1:
+        raise ValueError(f"min_leaf must be an integer >= 1, got {min_leaf}")
+    f = np.asarray(features).reshape(-1)
+    if not 1 <= len(f) <= 32:
+        raise ValueError(f"between 1 and 32 features are supported, got {len(f)}")
+    if not np.all(f == np.floor(f)) or f.min() < 0 or f.max() >= X.shape[1]:
+        raise ValueError(f"features must index the {X.shape[1]} columns of X, got {list(f)}")
+    f = [int(v) for v in f]
+    if len(set(f)) != len(f):
+        raise ValueError(f"features must be distinct, got {f}")
+    n = len(Y)
+    tr = None
+    if train is not None:
+        tr = np.asarray(train)
+        if tr.shape != (n,) or tr.dtype != np.bool_:
+            raise ValueError(f"train must be a boolean mask with one entry per row ({n})")
+        if not tr.any():
+            raise ValueError("the train mask leaves no training rows")
+    edges = []
+    for j in f:
+        u = np.unique(X[:, j])
+        if len(u) <= bins:
+            edges.append(u[1:])
+        else:
+            xs = np.sort(X[:, j])
+            edges.append(np.unique([xs[(k * n) // int(bins)] for k in range(1, int(bins))]))
+    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    rec, fin, e = policy_tree_from_scores(psi - float(cost), X[:, f], edges, tr, depth, min_leaf)
+    return PolicyTreeResult.make(method, rec, fin, f, edges, float(cost), int(depth),
+                                 held_out=train is not None, hipgraph=False, e=int(e),
+                                 min_leaf=int(min_leaf), bins=int(bins))
+
+
 def sensitivity_from_rows(psi, b, c, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0):
     """The sensitivity figures of per-row (psi, b, c), row by row in float64 -- written
     independently of the moment route of result.SensitivityResult: the SEs are

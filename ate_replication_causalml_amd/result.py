@@ -216,6 +216,126 @@ class CateResult:
                            "diagnostics": keep(self.diagnostics)}, default=str)
 
 
+def _policy_values(row, names):
+    """One evaluation set of a policy tree from its finalised row [20] (estimators/policy.py
+    ``policy_finalize``): value, treat_all and advantage with SE and 1.96 SE bounds, the share
+    treated, n and the leaf table of the structural leaves ``names`` ((slot, label) pairs)."""
+    v = [float(x) for x in row]
+    out = {}
+    for k, name in enumerate(("value", "treat_all", "advantage")):
+        a, s = v[2 * k], v[2 * k + 1]
+        out.update({name: a, f"{name}_se": s, f"{name}_lower_ci": a - Z * s,
+                    f"{name}_upper_ci": a + Z * s})
+    out["share_treated"] = v[6]
+    out["n"] = int(round(v[7])) if math.isfinite(v[7]) else -1
+    out["leaves"] = [{"leaf": label, "n": int(round(v[8 + 3 * s])) if math.isfinite(v[8 + 3 * s]) else -1,
+                      "action": act, "mean": v[9 + 3 * s], "se": v[10 + 3 * s]}
+                     for s, label, act in names]
+    return out
+
+
+@dataclass
+class PolicyTreeResult:
+    """An exact policy tree of depth <= 2 on per-row scores r = psi - cost: whom to treat.
+    ``nodes``: root, left and right child, each with the column of X it splits (``feature``,
+    None for a leaf), the bin ``t`` and the ``threshold`` (rows with x < threshold go left).
+    ``in_sample`` / ``held_out``: value = mean(pi r), treat_all = mean(r), advantage = value -
+    treat_all, each with SE and bounds, the share treated and the leaf table (n, action, mean
+    r, SE). The in-sample values are optimistic: the tree was chosen on those rows."""
+    method: str
+    nodes: list
+    actions: list                  # leaf actions LL, LR, RL, RR (a leaf node repeats its own)
+    in_sample: dict
+    held_out: dict | None
+    value_q: int                   # the training value in fixed-point units (S q of treated leaves)
+    n_train: int
+    features: list                 # columns of X, the index space of nodes[.]["feature"]
+    edges: list                    # per feature: the ascending split points
+    cost: float
+    depth: int
+    diagnostics: dict = field(default_factory=dict)
+
+    @classmethod
+    def make(cls, method, rec, fin, features, edges, cost, depth, held_out=False, **diag):
+        rec = [int(v) for v in rec]
+        edges = [[float(v) for v in ed] for ed in edges]
+        nan = not math.isfinite(float(fin[0][0]))
+        if nan:                    # a NaN fit never yields a tree that looks learned (the
+            rec = [-1] * 6 + [0] * 4 + [0, rec[11]]     # device path masks its record too)
+        nodes = []
+        for k, name in enumerate(("root", "left", "right")):
+            j, t = rec[2 * k], rec[2 * k + 1]
+            nodes.append({"node": name, "feature": features[j] if j >= 0 else None,
+                          "bin": t if j >= 0 else None,
+                          "threshold": edges[j][t] if j >= 0 else None})
+        acts = rec[6:10]
+        if rec[0] < 0:
+            names = [(0, "root", acts[0])]
+        else:
+            names = []
+            for side, tag in ((0, "L"), (1, "R")):
+                if rec[2 + 2 * side] < 0:
+                    names.append((2 * side, tag, acts[2 * side]))
+                else:
+                    names += [(2 * side, tag + "L", acts[2 * side]),
+                              (2 * side + 1, tag + "R", acts[2 * side + 1])]
+        diag = {"honest": bool(held_out), "nan": nan, **diag}
+        return cls(method, nodes, acts, _policy_values(fin[0], names),
+                   _policy_values(fin[1], names) if held_out else None, rec[10], rec[11],
+                   [int(f) for f in features], edges, float(cost), int(depth), diag)
+
+    @property
+    def value(self) -> float:
+        """The held-out value when there is a held-out set, else the (optimistic) in-sample one."""
+        return (self.held_out or self.in_sample)["value"]
+
+    def predict(self, X):
+        """The 0/1 action of every row of X (columns as in the fitted X), on the host."""
+        import numpy as np
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] <= max(self.features):
+            raise ValueError(f"X must be a matrix with more than {max(self.features)} columns")
+        root, acts = self.nodes[0], np.asarray(self.actions, dtype=np.int64)
+        if root["feature"] is None:
+            return np.full(len(X), acts[0], dtype=np.int64)
+        right = X[:, root["feature"]] >= root["threshold"]
+        down = np.zeros(len(X), dtype=bool)
+        for side in (0, 1):
+            ch = self.nodes[1 + side]
+            if ch["feature"] is not None:
+                down |= (right == bool(side)) & (X[:, ch["feature"]] >= ch["threshold"])
+        return acts[2 * right.astype(np.int64) + down.astype(np.int64)]
+
+    def table(self) -> str:
+        lines = [f"{self.method}: depth {self.depth}, cost {self.cost:g}, "
+                 f"{self.n_train} training rows"]
+        for nd in self.nodes:
+            lines.append(f"{nd['node']:>6s}: " + ("leaf" if nd["feature"] is None else
+                                                  f"x{nd['feature']} < {nd['threshold']:.6g}"))
+        for name, ev in (("in-sample (optimistic)", self.in_sample), ("held-out", self.held_out)):
+            if ev is None:
+                continue
+            lines.append(f"{name}: n {ev['n']}, share treated {ev['share_treated']:.4f}")
+            for k in ("value", "treat_all", "advantage"):
+                lines.append(f"{k:>12s} {ev[k]:9.4f} {ev[k + '_se']:9.4f} "
+                             f"{ev[k + '_lower_ci']:9.4f} {ev[k + '_upper_ci']:9.4f}")
+            lines.append(f"{'leaf':>12s} {'n':>9s} {'action':>6s} {'mean':>9s} {'SE':>9s}")
+            for lf in ev["leaves"]:
+                lines.append(f"{lf['leaf']:>12s} {lf['n']:9d} {lf['action']:6d} {lf['mean']:9.4f} "
+                             f"{lf['se']:9.4f}")
+        return "\n".join(lines)
+
+    def to_json(self):
+        keep = lambda d: {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v))
+                          for k, v in d.items()}
+        return json.dumps({"method": self.method, "nodes": self.nodes, "actions": self.actions,
+                           "in_sample": self.in_sample, "held_out": self.held_out,
+                           "value_q": self.value_q, "n_train": self.n_train,
+                           "features": self.features, "edges": self.edges, "cost": self.cost,
+                           "depth": self.depth, "diagnostics": keep(self.diagnostics)},
+                          default=str)
+
+
 # ------------------------------------------------------------ sensitivity to confounding
 # the 14 moments of the sensitivity pass (estimators/sensitivity.py, csrc/irm.hip), with
 # b = (y - g_w)^2, rr = w / e - (1 - w) / (1 - e), c = 2 (1 / e + 1 / (1 - e)) - rr^2
