@@ -31,14 +31,12 @@ import torch
 
 from .. import _native
 from ..ops.linalg import spd_solve
-from ..ops.panel import build_panel
 from ..parallel import rng
-from ..result import AteResult, CateResult, boot_rank
-from ..utils.graphs import estimator_graphs
-from .common import as_np, resolve_device
-from .gate import _SLAB_BYTES, check_boot, quantile_groups
-from .irm import check_cells, irm_finalize, irm_fit_phases, irm_scores
-from .lasso import _fold_ids
+from ..result import AteResult, CateResult
+from .common import as_np
+from .gate import _SLAB_BYTES, boot_crit, check_boot, multiplier_geometry, quantile_groups
+from .irm import (arm_split_panel, comm_counts, irm_finalize, irm_fit_phases, phase_scores,
+                  run_body, run_phases)
 
 DF_MAX = 32
 DEGREE_MAX = 3
@@ -156,19 +154,12 @@ def moments_geometry(ld: int) -> int:
 
 
 def boot_geometry(n_boot: int, df: int, ld: int):
-    """(threads per workgroup, stream blocks, workgroups along the rows) of pass 2: the
-    geometry of ``gate.boot_geometry``. Up to DF_REG basis functions the replicate sums stay
-    in registers and the [workgroup][basis function][replicate] partials are written once,
-    under gate's workspace cap; above that they are the kernel's working set, read and
-    written for every chunk, so the workspace is held to _SLAB_LIVE_BYTES (it stays in the
-    last-level cache) and a workgroup walks more chunks."""
-    nst = -(-n_boot // 128)
-    ch = 64 * ((min(nst, 8) + 1) // 2)
-    nby = -(-nst // (ch // 32))
-    nbx = min(-(-ld // ch), max(1, 1024 // nby))
-    cap = _SLAB_BYTES if df <= DF_REG else _SLAB_LIVE_BYTES
-    nbx = max(1, min(nbx, cap // (nby * df * 4 * ch * 8)))
-    return ch, nby, nbx
+    """``gate.multiplier_geometry`` of pass 2: a slot per basis function, an fp64 sum per
+    replicate. Up to DF_REG basis functions the replicate sums stay in registers and the
+    partials are written once, under gate's workspace cap; above that they are the kernel's
+    working set, read and written for every chunk, so the workspace is held to
+    _SLAB_LIVE_BYTES (it stays in the last-level cache) and a workgroup walks more chunks."""
+    return multiplier_geometry(n_boot, df, ld, 8, _SLAB_BYTES if df <= DF_REG else _SLAB_LIVE_BYTES)
 
 
 def _cpu_rows(psi, x, rid):
@@ -298,9 +289,7 @@ def cate_finalize(mom: torch.Tensor, boot: torch.Tensor, beta: torch.Tensor, gba
     G = gbasis.to(mom.device, torch.float64)
     cate = G @ beta
     se = torch.sqrt(((G @ Omega) * G).sum(dim=1).clamp(min=0))
-    t = (T @ (Minv.T @ G.T)) / se
-    tmax = t.abs().max(dim=1).values
-    crit = torch.sort(tmax).values[boot_rank(level, n_boot) - 1]
+    crit = boot_crit((T @ (Minv.T @ G.T)) / se, n_boot, level)
     overall = irm_finalize(torch.stack([head[1], head[2], head[0]]))
     return torch.cat([cate, se, crit.reshape(1), overall, head[:1], beta, Omega.reshape(-1)])
 
@@ -326,9 +315,6 @@ def cate_phases(pan, x, rid, knots, gbasis, degree: int, folds: int, lambda_rule
     check_boot(B, level)
     phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts)
 
-    def phase_scores(st):
-        return {**st, "psi": irm_scores(pan, st["coef"], clip, 2)}
-
     def phase_moments(st):
         return {**st, "mom": cate_moments(st["psi"], x, rid, knots, q)}
 
@@ -342,7 +328,7 @@ def cate_phases(pan, x, rid, knots, gbasis, degree: int, folds: int, lambda_rule
         return {**st, "fin": cate_finalize(st["mom"], st["boot"], st["beta"], gbasis, d, q, B,
                                            level)}
 
-    phases += [phase_scores, phase_moments]
+    phases += [phase_scores(pan, clip), phase_moments]
     if reduce is not None:
         phases.append(reduce("mom"))
     phases += [phase_beta, phase_boot]
@@ -410,20 +396,18 @@ def irm_cate_panel(pan, x: torch.Tensor, knots: torch.Tensor, degree: int, grid,
     else:
         kn = knots.cpu().numpy()
         gbasis = bspline_basis(check_grid(grid, kn[0], kn[-1]), knots.cpu(), q).to(pan.device)
-    st = None
-    for ph in cate_phases(pan, x, rid, knots, gbasis, q, folds, lambda_rule, clip, n_boot, level,
-                          seed, comm, seg_counts):
-        st = ph(st)
+    st = run_phases(cate_phases(pan, x, rid, knots, gbasis, q, folds, lambda_rule, clip, n_boot,
+                                level, seed, comm, seg_counts))
     return st["fin"], st["mom"], st["boot"], st.get("cv")
 
 
 def _cate_body(pan, x, rid, knots, gbasis, folds, lambda_rule, clip, degree, n_boot, level, seed,
                dist=None, counts=None):
     """The whole estimator as one device function (GraphCache captures it): fin | mom | boot."""
-    comm = dist.comm if dist is not None else None
+    comm, seg_counts = comm_counts(dist, counts)
     fin, mom, boot, _ = irm_cate_panel(pan, x, knots, degree, gbasis, folds, lambda_rule, clip,
                                        n_boot, level, seed, comm=comm, rid=rid, check=False,
-                                       seg_counts=None if counts is None else np.asarray(counts))
+                                       seg_counts=seg_counts)
     return torch.cat([fin, mom, boot])
 
 
@@ -462,8 +446,7 @@ def dml_irm_cate_lasso(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boo
     grid size, n_boot); x, the row ids, the knots and the grid's basis matrix are graph
     inputs, so another column in the same layout replays it. keep_boot: the result's
     ``boot`` holds the raw replicate sums T [n_boot, df], M and the meat."""
-    dev = resolve_device(device)
-    Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
+    Yn, Xn = as_np(Y), as_np(X)
     check_boot(n_boot, level)
     check_basis(df if knots is None else len(knots) - degree - 1, degree)
     n_boot, q = int(n_boot), int(degree)
@@ -478,8 +461,6 @@ def dml_irm_cate_lasso(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boo
                              f"got shape {np.shape(by)}")
     if not np.isfinite(xn).all():
         raise ValueError("the covariate of the curve must be finite")
-    if not np.isin(Wn, (0.0, 1.0)).all():
-        raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
     sharded = dist is not None and dist.world > 1
     # every rank needs the same knots and grid: the covariate of all shards, gathered
     x_all = dist.gather_rows(torch.as_tensor(xn)).numpy() if sharded else xn
@@ -494,33 +475,15 @@ def dml_irm_cate_lasso(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boo
     d = len(kn) - q - 1
     gr = check_grid(default_grid(x_all) if grid is None else grid, kn[0], kn[-1])
     m = len(gr)
-    scount = np.bincount(np.searchsorted(kn[q + 1:d], xn, side="right"),
-                         minlength=d - q).astype(np.float64)
-    fid = _fold_ids(len(Yn), folds, seed, 0, dist)
-    seg = 2 * np.asarray(fid, dtype=np.int64) + Wn.astype(np.int64)
-    counts = np.bincount(seg, minlength=2 * folds).astype(np.float64)
-    if sharded:
-        t = torch.as_tensor(np.concatenate([counts, scount])).to(dev)
-        dist.sum_(t)
-        t = t.cpu().numpy()
-        counts, scount = t[:2 * folds], t[2 * folds:]
-    check_spans(scount)
-    check_cells(counts, folds)
-    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev)
-    real = pan.row_index >= 0
+    scount = np.bincount(np.searchsorted(kn[q + 1:d], xn, side="right"), minlength=d - q)
+    pan, counts, _, _, rid = arm_split_panel(Y, W, X, folds, seed, dtype, device, dist,
+                                             extra_counts=scount, check_extra=check_spans)
     x = pan.gather_rows(torch.as_tensor(xn))
-    rid = torch.where(real, pan.row_index + (dist.row_offset if dist is not None else 0),
-                      torch.full_like(pan.row_index, -1))
     knt = torch.from_numpy(kn).to(pan.device)
     gbasis = bspline_basis(gr, kn, q).to(pan.device)
-    args = (folds, lambda_rule, float(clip), q, n_boot, float(level), int(seed), dist,
-            tuple(counts.tolist()))
-    g = False
-    if graph and (dist is None or dist.capturable) and pan.data.is_cuda:
-        out, g = estimator_graphs.run("dml_irm_cate", _cate_body, (pan, x, rid, knt, gbasis),
-                                      *args)
-    else:
-        out = _cate_body(pan, x, rid, knt, gbasis, *args)
+    out, g = run_body("dml_irm_cate", _cate_body, (pan, x, rid, knt, gbasis), folds, lambda_rule,
+                      float(clip), q, n_boot, float(level), int(seed), dist,
+                      tuple(counts.tolist()), graph=graph, dist=dist)
     v = out.detach().double().cpu().numpy()
     nf = fin_size(d, m)
     cate, se, crit, o_ate, o_se, n, beta, omega = read_fin(v[:nf], d, m)

@@ -16,6 +16,9 @@ accumulates all B x G replicate sums with the multipliers generated in registers
 (csrc/gate.hip): A = S xi psi and Z = S xi, so S xi (psi - theta_g) = A - theta_g Z and no
 group mean is needed inside the pass. Multipliers are keyed by the global row id
 (parallel/rng.rademacher): the same draws at every world size and in every panel order.
+The launch geometry (:func:`multiplier_geometry`) and the critical value (:func:`boot_crit`)
+are shared with the CATE curve (estimators/cate.py), as the device core is
+(csrc/boot_common.hpp).
 """
 from __future__ import annotations
 
@@ -23,17 +26,15 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..ops.panel import build_panel
 from ..parallel import rng
 from ..result import AteResult, GateResult, boot_rank
-from ..utils.graphs import estimator_graphs
-from .common import as_np, resolve_device
-from .irm import check_cells, irm_finalize, irm_fit_phases, irm_scores
-from .lasso import _fold_ids
+from .common import as_np
+from .irm import (arm_split_panel, comm_counts, irm_finalize, irm_fit_phases, mean_se,
+                  phase_scores, run_body, run_phases)
 
 N_GROUPS_MAX = 64
 N_BOOT_MAX = 4096
-_SLAB_BYTES = 64 << 20      # cap of the bootstrap kernel's partial workspace
+_SLAB_BYTES = 64 << 20      # cap of the bootstrap kernels' partial workspace
 
 
 def check_boot(n_boot, level=0.95):
@@ -52,17 +53,30 @@ def check_groups(counts):
         raise ValueError(f"group {int(g)} has {int(c[g])} row(s): every group needs at least 2")
 
 
-def boot_geometry(n_boot: int, n_groups: int, ld: int):
-    """(threads per workgroup, stream blocks, workgroups along the rows) of csrc/gate.hip:
-    32 threads per Philox stream of 128 replicates, up to 8 streams per workgroup; about
-    1024 workgroups in all, fewer when the [workgroup][group][replicate] partials would
-    exceed the workspace cap."""
+def multiplier_geometry(n_boot: int, slots: int, ld: int, bytes_per_item: int, cap: int):
+    """(threads per workgroup, stream blocks, workgroups along the rows) of the multiplier
+    bootstrap kernels, the host side of ``geometry`` in csrc/boot_common.hpp: 32 threads per
+    Philox stream of 128 replicates, up to 8 streams per workgroup; about 1024 workgroups in
+    all, fewer when the [workgroup][slot][replicate] partials of ``bytes_per_item`` bytes
+    each would exceed ``cap`` bytes."""
     nst = -(-n_boot // 128)
     ch = 64 * ((min(nst, 8) + 1) // 2)
     nby = -(-nst // (ch // 32))
     nbx = min(-(-ld // ch), max(1, 1024 // nby))
-    nbx = max(1, min(nbx, _SLAB_BYTES // (nby * n_groups * 4 * ch * 12)))
+    nbx = max(1, min(nbx, cap // (nby * slots * 4 * ch * bytes_per_item)))
     return ch, nby, nbx
+
+
+def boot_geometry(n_boot: int, n_groups: int, ld: int):
+    """:func:`multiplier_geometry` of csrc/gate.hip: a slot per group, an fp64 sum and an
+    integer count per replicate."""
+    return multiplier_geometry(n_boot, n_groups, ld, 12, _SLAB_BYTES)
+
+
+def boot_crit(t: torch.Tensor, n_boot: int, level: float) -> torch.Tensor:
+    """The critical value of a joint band from the replicates' statistics t [B, points]: the
+    ceil(level B)-th smallest of max |t[b, .]|. Device ops only."""
+    return torch.sort(t.abs().max(dim=1).values).values[boot_rank(level, n_boot) - 1]
 
 
 def group_boot(psi: torch.Tensor, gid: torch.Tensor, rid: torch.Tensor, n_groups: int,
@@ -131,11 +145,8 @@ def gate_finalize(buf: torch.Tensor, n_groups: int, n_boot: int, level: float = 
     moments."""
     mom, A, Z = split_boot(buf, n_groups, n_boot)
     n, s1, s2 = mom[:, 0], mom[:, 1], mom[:, 2]
-    theta = s1 / n
-    se = torch.sqrt(((s2 - s1 * s1 / n) / (n - 1) / n).clamp(min=0))
-    t = (A - theta * Z) / (n * se)
-    tmax = t.abs().max(dim=1).values
-    crit = torch.sort(tmax).values[boot_rank(level, n_boot) - 1]
+    theta, se = mean_se(s1, s2, n)
+    crit = boot_crit((A - theta * Z) / (n * se), n_boot, level)
     overall = irm_finalize(torch.stack([s1.sum(), s2.sum(), n.sum()]))
     return torch.cat([theta, se, n, crit.reshape(1), overall])
 
@@ -180,16 +191,13 @@ def gate_phases(pan, gid, rid, n_groups: int, folds: int, lambda_rule="min", cli
     check_boot(B, level)
     phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts)
 
-    def phase_scores(st):
-        return {**st, "psi": irm_scores(pan, st["coef"], clip, 2)}
-
     def phase_boot(st):
         return {**st, "boot": group_boot(st["psi"], gid, rid, G, B, seed)}
 
     def phase_final(st):
         return {**st, "fin": gate_finalize(st["boot"], G, B, level)}
 
-    phases += [phase_scores, phase_boot]
+    phases += [phase_scores(pan, clip), phase_boot]
     if reduce is not None:
         phases.append(reduce("boot"))
     phases.append(phase_final)
@@ -228,20 +236,17 @@ def irm_gate_panel(pan, gid: torch.Tensor, folds: int, lambda_rule="min", clip=0
         check_groups(group_counts(gid, n_groups, comm))
     if rid is None:
         rid = pan.row_index
-    st = None
-    for ph in gate_phases(pan, gid, rid, n_groups, folds, lambda_rule, clip, n_boot, level, seed,
-                          comm, seg_counts):
-        st = ph(st)
+    st = run_phases(gate_phases(pan, gid, rid, n_groups, folds, lambda_rule, clip, n_boot, level,
+                                seed, comm, seg_counts))
     return st["fin"], st["boot"], st.get("cv")
 
 
 def _gate_body(pan, gid, rid, folds, lambda_rule, clip, n_groups, n_boot, level, seed, dist=None,
                counts=None):
     """The whole estimator as one device function (GraphCache captures it): fin | boot."""
-    comm = dist.comm if dist is not None else None
+    comm, seg_counts = comm_counts(dist, counts)
     fin, boot, _ = irm_gate_panel(pan, gid, folds, lambda_rule, clip, n_boot, level, seed,
-                                  comm=comm, rid=rid, n_groups=n_groups,
-                                  seg_counts=None if counts is None else np.asarray(counts))
+                                  comm=comm, rid=rid, n_groups=n_groups, seg_counts=seg_counts)
     return torch.cat([fin, boot])
 
 
@@ -257,18 +262,14 @@ def dml_irm_gate_lasso(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", c
     graph: as ``dml_irm_lasso``, one captured hipGraph on a GPU; the group codes are a graph
     input, so a call with other groups in the same panel layout replays it. keep_boot: the
     result's ``boot`` holds the raw replicate sums A, Z [n_boot, G]."""
-    dev = resolve_device(device)
-    Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
     check_boot(n_boot, level)
     n_boot = int(n_boot)
     gl = np.asarray(groups)
-    if gl.ndim != 1 or len(gl) != len(Yn):
-        raise ValueError(f"groups must be a vector with one label per row ({len(Yn)}), "
+    rows = len(as_np(Y))
+    if gl.ndim != 1 or len(gl) != rows:
+        raise ValueError(f"groups must be a vector with one label per row ({rows}), "
                          f"got shape {gl.shape}")
-    if not np.isin(Wn, (0.0, 1.0)).all():
-        raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
-    sharded = dist is not None and dist.world > 1
-    if sharded:
+    if dist is not None and dist.world > 1:
         # every rank needs the same codes: the labels of all shards, gathered
         labels_all = dist.gather_rows(torch.as_tensor(gl)).numpy()
         labels = np.unique(labels_all)
@@ -278,29 +279,14 @@ def dml_irm_gate_lasso(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", c
     G = len(labels)
     if G > N_GROUPS_MAX:
         raise ValueError(f"at most {N_GROUPS_MAX} groups are supported, got {G}")
-    gcount = np.bincount(codes, minlength=G).astype(np.float64)
-    fid = _fold_ids(len(Yn), folds, seed, 0, dist)
-    seg = 2 * np.asarray(fid, dtype=np.int64) + Wn.astype(np.int64)
-    counts = np.bincount(seg, minlength=2 * folds).astype(np.float64)
-    if sharded:
-        t = torch.as_tensor(np.concatenate([counts, gcount])).to(dev)
-        dist.sum_(t)
-        t = t.cpu().numpy()
-        counts, gcount = t[:2 * folds], t[2 * folds:]
-    check_groups(gcount)
-    check_cells(counts, folds)
-    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev)
-    real = pan.row_index >= 0
-    gid = torch.where(real, pan.gather_rows(torch.as_tensor(codes.astype(np.int32))),
+    pan, counts, _, _, rid = arm_split_panel(
+        Y, W, X, folds, seed, dtype, device, dist,
+        extra_counts=np.bincount(codes, minlength=G), check_extra=check_groups)
+    gid = torch.where(rid >= 0, pan.gather_rows(torch.as_tensor(codes.astype(np.int32))),
                       torch.full((pan.ld,), -1, dtype=torch.int32, device=pan.device))
-    rid = pan.row_index + (dist.row_offset if dist is not None else 0)
-    args = (folds, lambda_rule, float(clip), G, n_boot, float(level), int(seed), dist,
-            tuple(counts.tolist()))
-    g = False
-    if graph and (dist is None or dist.capturable) and pan.data.is_cuda:
-        out, g = estimator_graphs.run("dml_irm_gate", _gate_body, (pan, gid, rid), *args)
-    else:
-        out = _gate_body(pan, gid, rid, *args)
+    out, g = run_body("dml_irm_gate", _gate_body, (pan, gid, rid), folds, lambda_rule,
+                      float(clip), G, n_boot, float(level), int(seed), dist,
+                      tuple(counts.tolist()), graph=graph, dist=dist)
     v = out.detach().double().cpu().numpy()
     theta, se, n = v[:G], v[G:2 * G], v[2 * G:3 * G]
     crit, o_ate, o_se = v[3 * G:3 * G + 3]

@@ -15,6 +15,13 @@ pass (K01) then yields per-(fold, arm) Grams; the fold Grams of the propensity p
 their pairwise sums. All 3 K (K + 1) path problems (3 nuisances x K outer folds x (1 full +
 K - 1 inner CV)) run in ONE ``ate_enet_path`` launch (``ops/enet.cv_enet_gaussian(full_y=)``),
 and one fused pass over the panel (csrc/irm.hip) accumulates the 8 score moments.
+
+The estimators on the same score (gate, cate, policy, sensitivity) share what lives here: the
+score pass in its three forms (:func:`irm_score_moments`, :func:`irm_sens_moments`,
+:func:`irm_scores` -- one CPU twin ``_score_terms``, one launcher ``_score_launch``), the
+front end of every ``dml_irm_*`` function (:func:`arm_split_panel`, :func:`run_body`,
+:func:`comm_counts`), the fit and score phases (:func:`irm_fit_phases`, :func:`phase_scores`,
+:func:`run_phases`) and the n - 1 variance rule (:func:`mean_se`).
 """
 from __future__ import annotations
 
@@ -26,7 +33,7 @@ from ..ops.devconst import const
 from ..ops.enet import cv_enet_gaussian
 from ..ops.gram import gram
 from ..ops.panel import build_panel, dtype_code
-from ..result import AteResult
+from ..result import SENS_MOMENTS, AteResult
 from ..utils.graphs import estimator_graphs
 from .common import as_np, resolve_device
 from .lasso import _fold_ids, _tri_index, allreduce_sym_, global_seg_counts
@@ -42,14 +49,8 @@ def _yw_columns(pan):
     return pan.cols["Y"], -1, pan.cols["W"], -1
 
 
-def irm_score_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
-                      nbx: int | None = None) -> torch.Tensor:
-    """Fused held-out AIPW score pass -> the 8 fp64 moments (N_MOMENTS).
-
-    coef: [nfold, 3, p+1] fp64, rows (g0, g1, m), intercept first; segment s of the panel
-    uses block ``s // segs_per_fold`` (2: the arm-split layout; 1: a plain K-fold panel).
-    W is read from the panel on every row. GPU: csrc/irm.hip (``nbx`` blocks per segment);
-    CPU: the float64 torch twin below, the kernel's oracle."""
+def _score_args(pan, coef, segs_per_fold):
+    """The argument checks of the score pass; returns p, the number of covariates."""
     nseg = pan.nseg
     nfold = coef.shape[0]
     if segs_per_fold < 1 or nfold * segs_per_fold < nseg:
@@ -58,45 +59,106 @@ def irm_score_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold
     p = len(pan.xcols)
     if tuple(coef.shape[1:]) != (3, p + 1):
         raise ValueError(f"coef must be [nfold, 3, {p + 1}], got {tuple(coef.shape)}")
+    return p
+
+
+def _score_terms(pan, coef, segs_per_fold):
+    """The float64 CPU twin of the score pass (the kernels' oracle): per segment
+    ``(r0, r1, v, y, w, g0, g1, m)`` -- its row range, the mask of its real rows, and over
+    those rows the targets, the two outcome regressions and the unclipped propensity."""
+    _score_args(pan, coef, segs_per_fold)
     y0, y1, w0, w1 = _yw_columns(pan)
-    if not pan.data.is_cuda:
-        X = pan.colmajor().double()
-        c = coef.double()
-        mom = torch.zeros(N_MOMENTS, dtype=torch.float64)
-        lo, hi = clip, 1.0 - clip
-        for s in range(nseg):
-            r0, r1 = (int(v) for v in pan.seg_bounds[s])
-            Xs = X[:, r0:r1]
-            v = Xs[pan.cols["one"]] != 0
-            xs = Xs[pan.xcols][:, v]
-            y = Xs[y0][v] + (Xs[y1][v] if y1 >= 0 else 0.0)
-            w = Xs[w0][v] + (Xs[w1][v] if w1 >= 0 else 0.0)
-            k = s // segs_per_fold
-            g0 = c[k, 0, 0] + c[k, 0, 1:] @ xs
-            g1 = c[k, 1, 0] + c[k, 1, 1:] @ xs
-            m = c[k, 2, 0] + c[k, 2, 1:] @ xs
-            e = m.clamp(lo, hi)
-            psi = g1 - g0 + w * (y - g1) / e - (1.0 - w) * (y - g0) / (1.0 - e)
-            one = torch.ones_like(psi)
-            mom += torch.stack([psi.sum(), (psi * psi).sum(), one.sum(),
-                                ((m < lo) | (m > hi)).double().sum(),
-                                (w * (y - g1) ** 2).sum(), ((1.0 - w) * (y - g0) ** 2).sum(),
-                                ((w - m) ** 2).sum(), w.sum()])
-        return mom
+    X = pan.colmajor().double()
+    c = coef.double()
+    for s in range(pan.nseg):
+        r0, r1 = (int(v) for v in pan.seg_bounds[s])
+        Xs = X[:, r0:r1]
+        v = Xs[pan.cols["one"]] != 0
+        xs = Xs[pan.xcols][:, v]
+        y = Xs[y0][v] + (Xs[y1][v] if y1 >= 0 else 0.0)
+        w = Xs[w0][v] + (Xs[w1][v] if w1 >= 0 else 0.0)
+        k = s // segs_per_fold
+        yield (r0, r1, v, y, w, c[k, 0, 0] + c[k, 0, 1:] @ xs, c[k, 1, 0] + c[k, 1, 1:] @ xs,
+               c[k, 2, 0] + c[k, 2, 1:] @ xs)
+
+
+def aipw_psi(y, w, g0, g1, e):
+    """The AIPW score with the clipped propensity ``e`` (the module docstring's psi)."""
+    return g1 - g0 + w * (y - g1) / e - (1.0 - w) * (y - g0) / (1.0 - e)
+
+
+def _score_launch(name, pan, coef, clip, segs_per_fold, nbx, n_out, moments):
+    """One instantiation of the fused score pass (csrc/irm.hip entry point ``name``) with
+    ``nbx`` blocks per segment. ``moments``: the entry point sums ``n_out`` moments (a
+    ``partial`` workspace, then the result); otherwise it writes ``n_out`` = ld row scores."""
+    p = _score_args(pan, coef, segs_per_fold)
+    y0, y1, w0, w1 = _yw_columns(pan)
     dev = pan.device
     xc = const(pan.xcols, torch.int32, dev)
     segs = const(np.asarray(pan.seg_bounds, dtype=np.int64), torch.int64, dev)
     if nbx is None:
         # bf16: 2048 rows per block; enough blocks per segment to fill 256 CUs several times
         nbx = 512 if pan.dtype == torch.bfloat16 else 256
-    part = torch.empty(nseg * nbx * N_MOMENTS, dtype=torch.float64, device=dev)
-    mom = torch.empty(N_MOMENTS, dtype=torch.float64, device=dev)
+    out = torch.empty(n_out, dtype=torch.float64, device=dev)
+    bufs = (out,)
+    if moments:
+        bufs = (torch.empty(pan.nseg * nbx * n_out, dtype=torch.float64, device=dev), out)
     c = coef.double().contiguous()
     cs, bs = pan.strides()
-    _native.call("ate_irm_score_moments", dtype_code(pan.data), pan.data.data_ptr(), cs, bs,
-                 xc.data_ptr(), p, segs.data_ptr(), nseg, segs_per_fold, c.data_ptr(), y0, y1,
-                 w0, w1, pan.cols["one"], float(clip), nbx, part.data_ptr(), mom.data_ptr(),
+    _native.call(name, dtype_code(pan.data), pan.data.data_ptr(), cs, bs, xc.data_ptr(), p,
+                 segs.data_ptr(), pan.nseg, segs_per_fold, c.data_ptr(), y0, y1, w0, w1,
+                 pan.cols["one"], float(clip), nbx, *(b.data_ptr() for b in bufs),
                  torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def irm_score_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
+                      nbx: int | None = None) -> torch.Tensor:
+    """Fused held-out AIPW score pass -> the 8 fp64 moments (N_MOMENTS).
+
+    coef: [nfold, 3, p+1] fp64, rows (g0, g1, m), intercept first; segment s of the panel
+    uses block ``s // segs_per_fold`` (2: the arm-split layout; 1: a plain K-fold panel).
+    W is read from the panel on every row. GPU: csrc/irm.hip (``nbx`` blocks per segment);
+    CPU: the float64 torch twin (:func:`_score_terms`), the kernel's oracle."""
+    if pan.data.is_cuda:
+        return _score_launch("ate_irm_score_moments", pan, coef, clip, segs_per_fold, nbx,
+                             N_MOMENTS, True)
+    mom = torch.zeros(N_MOMENTS, dtype=torch.float64)
+    lo, hi = clip, 1.0 - clip
+    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
+        psi = aipw_psi(y, w, g0, g1, m.clamp(lo, hi))
+        one = torch.ones_like(psi)
+        mom += torch.stack([psi.sum(), (psi * psi).sum(), one.sum(),
+                            ((m < lo) | (m > hi)).double().sum(),
+                            (w * (y - g1) ** 2).sum(), ((1.0 - w) * (y - g0) ** 2).sum(),
+                            ((w - m) ** 2).sum(), w.sum()])
+    return mom
+
+
+def irm_sens_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
+                     nbx: int | None = None) -> torch.Tensor:
+    """The pass of :func:`irm_score_moments` -- same arguments, same dot products, same psi --
+    accumulating the 14 fp64 moments of the sensitivity analysis (``result.SENS_MOMENTS``;
+    estimators/sensitivity.py). GPU: csrc/irm.hip ``ate_irm_sens_moments`` (for the same
+    ``nbx`` S psi, S psi^2, n, n_clipped and n_treated carry the bits of
+    ``irm_score_moments``); CPU: the float64 torch twin."""
+    if pan.data.is_cuda:
+        return _score_launch("ate_irm_sens_moments", pan, coef, clip, segs_per_fold, nbx,
+                             len(SENS_MOMENTS), True)
+    mom = torch.zeros(len(SENS_MOMENTS), dtype=torch.float64)
+    lo, hi = clip, 1.0 - clip
+    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
+        e = m.clamp(lo, hi)
+        psi = aipw_psi(y, w, g0, g1, e)
+        b = torch.where(w != 0, (y - g1) ** 2, (y - g0) ** 2)
+        rr = w / e - (1.0 - w) / (1.0 - e)
+        cc = 2.0 * (1.0 / e + 1.0 / (1.0 - e)) - rr * rr
+        one = torch.ones_like(psi)
+        mom += torch.stack([psi.sum(), (psi * psi).sum(), one.sum(),
+                            ((m < lo) | (m > hi)).double().sum(),
+                            b.sum(), (b * b).sum(), cc.sum(), (cc * cc).sum(),
+                            (psi * b).sum(), (psi * cc).sum(), (b * cc).sum(),
+                            y.sum(), (y * y).sum(), w.sum()])
     return mom
 
 
@@ -105,59 +167,27 @@ def irm_scores(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int =
     """The per-row AIPW scores psi [ld] (fp64, panel row order, 0 on padding rows): the pass
     of :func:`irm_score_moments` -- same arguments, same dot products, same psi -- writing
     every row's score instead of summing moments (csrc/irm.hip ``ate_irm_scores``; CPU: the
-    float64 torch twin). Input of the grouped multiplier bootstrap (estimators/gate.py)."""
-    nseg = pan.nseg
-    nfold = coef.shape[0]
-    if segs_per_fold < 1 or nfold * segs_per_fold < nseg:
-        raise ValueError(f"{nseg} segments at {segs_per_fold} per fold need "
-                         f"{-(-nseg // max(segs_per_fold, 1))} coefficient blocks, got {nfold}")
-    p = len(pan.xcols)
-    if tuple(coef.shape[1:]) != (3, p + 1):
-        raise ValueError(f"coef must be [nfold, 3, {p + 1}], got {tuple(coef.shape)}")
-    y0, y1, w0, w1 = _yw_columns(pan)
-    if not pan.data.is_cuda:
-        X = pan.colmajor().double()
-        c = coef.double()
-        psi = torch.zeros(pan.ld, dtype=torch.float64)
-        for s in range(nseg):
-            r0, r1 = (int(v) for v in pan.seg_bounds[s])
-            Xs = X[:, r0:r1]
-            v = Xs[pan.cols["one"]] != 0
-            xs = Xs[pan.xcols][:, v]
-            y = Xs[y0][v] + (Xs[y1][v] if y1 >= 0 else 0.0)
-            w = Xs[w0][v] + (Xs[w1][v] if w1 >= 0 else 0.0)
-            k = s // segs_per_fold
-            g0 = c[k, 0, 0] + c[k, 0, 1:] @ xs
-            g1 = c[k, 1, 0] + c[k, 1, 1:] @ xs
-            e = (c[k, 2, 0] + c[k, 2, 1:] @ xs).clamp(clip, 1.0 - clip)
-            seg = psi[r0:r1]
-            seg[v] = g1 - g0 + w * (y - g1) / e - (1.0 - w) * (y - g0) / (1.0 - e)
-        return psi
-    bounds = np.asarray(pan.seg_bounds, dtype=np.int64)
-    if bounds[0, 0] != 0 or bounds[-1, 1] != pan.ld or np.any(bounds[1:, 0] != bounds[:-1, 1]):
-        raise ValueError("the panel's segments must tile [0, ld): every row gets a score")
-    dev = pan.device
-    xc = const(pan.xcols, torch.int32, dev)
-    segs = const(bounds, torch.int64, dev)
-    if nbx is None:
-        nbx = 512 if pan.dtype == torch.bfloat16 else 256
-    psi = torch.empty(pan.ld, dtype=torch.float64, device=dev)
-    c = coef.double().contiguous()
-    cs, bs = pan.strides()
-    _native.call("ate_irm_scores", dtype_code(pan.data), pan.data.data_ptr(), cs, bs,
-                 xc.data_ptr(), p, segs.data_ptr(), nseg, segs_per_fold, c.data_ptr(), y0, y1,
-                 w0, w1, pan.cols["one"], float(clip), nbx, psi.data_ptr(),
-                 torch.cuda.current_stream().cuda_stream)
+    float64 torch twin). Input of the estimators on the scores (gate, cate, policy)."""
+    if pan.data.is_cuda:
+        bounds = np.asarray(pan.seg_bounds, dtype=np.int64)
+        if bounds[0, 0] != 0 or bounds[-1, 1] != pan.ld or np.any(bounds[1:, 0] != bounds[:-1, 1]):
+            raise ValueError("the panel's segments must tile [0, ld): every row gets a score")
+        return _score_launch("ate_irm_scores", pan, coef, clip, segs_per_fold, nbx, pan.ld, False)
+    psi = torch.zeros(pan.ld, dtype=torch.float64)
+    for r0, r1, v, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
+        psi[r0:r1][v] = aipw_psi(y, w, g0, g1, m.clamp(clip, 1.0 - clip))
     return psi
 
 
+def mean_se(s1, s2, n):
+    """(mean, SE) from S x, S x^2 and n: SE^2 = the sample variance (the n - 1 rule) over n,
+    clamped at 0. Device tensors in and out, no host sync (capturable)."""
+    return s1 / n, torch.sqrt(((s2 - s1 * s1 / n) / (n - 1) / n).clamp(min=0))
+
+
 def irm_finalize(mom: torch.Tensor) -> torch.Tensor:
-    """[theta, SE] from the score moments: theta = S psi / n, SE^2 = the sample variance of
-    psi over n (clamped at 0). Device tensors in and out, no host sync (capturable)."""
-    n = mom[2]
-    theta = mom[0] / n
-    var = ((mom[1] - mom[0] * mom[0] / n) / (n - 1) / n).clamp(min=0)
-    return torch.stack([theta, torch.sqrt(var)])
+    """[theta, SE] from the score moments: theta = S psi / n, SE by :func:`mean_se`."""
+    return torch.stack(mean_se(mom[0], mom[1], mom[2]))
 
 
 def check_cells(counts, folds: int):
@@ -269,6 +299,22 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
     return phases, (reduce if dist else None)
 
 
+def phase_scores(pan, clip):
+    """The phase after :func:`irm_fit_phases` of every estimator on the per-row scores:
+    state "psi" [ld] (csrc/irm.hip ``ate_irm_scores``)."""
+    def f(st):
+        return {**st, "psi": irm_scores(pan, st["coef"], clip, 2)}
+    return f
+
+
+def run_phases(phases) -> dict:
+    """Run a phase list eagerly to its final state."""
+    st = None
+    for ph in phases:
+        st = ph(st)
+    return st
+
+
 def irm_crossfit_panel(pan, folds: int, lambda_rule="min", clip=0.01, comm=None,
                        seg_counts=None):
     """DML-IRM on an arm-split fold panel (segment 2k + a = fold k, W = a; from host arrays
@@ -279,17 +325,65 @@ def irm_crossfit_panel(pan, folds: int, lambda_rule="min", clip=0.01, comm=None,
     segment; the Gram stack and the score moments are all-reduced. seg_counts: global rows
     per segment (one all-reduce when omitted). A truncated CV fold path NaN-poisons the
     picked coefficients (ops/enet), and through them res."""
-    st = None
-    for ph in irm_phases(pan, folds, lambda_rule, clip, comm, seg_counts):
-        st = ph(st)
+    st = run_phases(irm_phases(pan, folds, lambda_rule, clip, comm, seg_counts))
     return st["res"], st["mom"], st.get("cv")
+
+
+# ---------------------------------------------------------------- the shared front end
+def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts=None,
+                    check_extra=None):
+    """The prologue of every ``dml_irm_*`` estimator: the binary-W check, the fold ids, the
+    (global) rows per (fold, arm) cell and the arm-split panel (segment 2k + a = fold k,
+    W = a) on ``device``. Returns (pan, counts [2K], extra, n_total, rid).
+
+    extra_counts: further local counts of the caller (rows per group, per span, ...). Over
+    row shards they are summed in the one all-reduce that sums the cell counts, come back as
+    ``extra`` and are handed to ``check_extra`` before the panel is built. rid: the rows'
+    global ids in panel row order (the key of the bootstrap multipliers), -1 on padding."""
+    dev = resolve_device(device)
+    Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
+    if not np.isin(Wn, (0.0, 1.0)).all():
+        raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
+    fid = _fold_ids(len(Yn), folds, seed, 0, dist)
+    seg = 2 * np.asarray(fid, dtype=np.int64) + Wn.astype(np.int64)
+    counts = np.bincount(seg, minlength=2 * folds).astype(np.float64)
+    extra = None if extra_counts is None else np.asarray(extra_counts, dtype=np.float64)
+    if dist is not None and dist.world > 1:
+        t = torch.as_tensor(counts if extra is None else np.concatenate([counts, extra])).to(dev)
+        dist.sum_(t)
+        t = t.cpu().numpy()
+        counts, extra = t[:2 * folds], None if extra is None else t[2 * folds:]
+    if check_extra is not None:
+        check_extra(extra)
+    check_cells(counts, folds)
+    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev)
+    rid = torch.where(pan.row_index >= 0,
+                      pan.row_index + (dist.row_offset if dist is not None else 0),
+                      torch.full_like(pan.row_index, -1))
+    return pan, counts, extra, (dist.n_total if dist is not None else len(Yn)), rid
+
+
+def comm_counts(dist, counts):
+    """(comm, seg_counts) of a ``*_panel`` call from a body's trailing (dist, counts)."""
+    return (dist.comm if dist is not None else None,
+            None if counts is None else np.asarray(counts))
+
+
+def run_body(name, body, tensors, *args, graph=True, dist=None):
+    """``body(*tensors, *args)`` as one captured hipGraph (``estimator_graphs`` entry
+    ``name``: first call of a layout eager, captured on the second, replayed after) when
+    ``graph`` is set, the panel ``tensors[0]`` is on a GPU and the collectives of ``dist`` can
+    be captured; otherwise a direct call. Returns (out, replayed)."""
+    if graph and (dist is None or dist.capturable) and tensors[0].data.is_cuda:
+        return estimator_graphs.run(name, body, tensors, *args)
+    return body(*tensors, *args), False
 
 
 def _irm_body(pan, folds, lambda_rule, clip, dist=None, counts=None):
     """The whole cross-fit as one device function (GraphCache captures it): [res, mom]."""
-    comm = dist.comm if dist is not None else None
+    comm, seg_counts = comm_counts(dist, counts)
     res, mom, _ = irm_crossfit_panel(pan, folds, lambda_rule, clip, comm=comm,
-                                     seg_counts=None if counts is None else np.asarray(counts))
+                                     seg_counts=seg_counts)
     return torch.cat([res, mom])
 
 
@@ -305,27 +399,9 @@ def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
     hipGraph (first call of a panel layout eager, captured on the second, replayed after).
     diagnostics: n, n_clipped (propensities outside [clip, 1-clip]), n_treated, the held-out
     RMSE of the three nuisances, hipgraph."""
-    dev = resolve_device(device)
-    Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
-    if not np.isin(Wn, (0.0, 1.0)).all():
-        raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
-    fid = _fold_ids(len(Yn), folds, seed, 0, dist)
-    seg = 2 * np.asarray(fid, dtype=np.int64) + Wn.astype(np.int64)
-    local = np.bincount(seg, minlength=2 * folds).astype(np.float64)
-    counts = local
-    if dist is not None and dist.world > 1:
-        t = torch.as_tensor(local).to(dev)
-        dist.sum_(t)
-        counts = t.cpu().numpy()
-    check_cells(counts, folds)
-    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev)
-    n = dist.n_total if dist is not None else len(Yn)
-    g = False
-    if graph and (dist is None or dist.capturable) and pan.data.is_cuda:
-        out, g = estimator_graphs.run("dml_irm", _irm_body, (pan,), folds, lambda_rule,
-                                      float(clip), dist, tuple(counts.tolist()))
-    else:
-        out = _irm_body(pan, folds, lambda_rule, clip, dist, counts)
+    pan, counts, _, n, _ = arm_split_panel(Y, W, X, folds, seed, dtype, device, dist)
+    out, g = run_body("dml_irm", _irm_body, (pan,), folds, lambda_rule, float(clip), dist,
+                      tuple(counts.tolist()), graph=graph, dist=dist)
     v = out.detach().double().cpu().numpy()
     mom = v[2:]
     nt = mom[7]

@@ -33,12 +33,11 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..ops.panel import build_panel
 from ..result import PolicyTreeResult
-from ..utils.graphs import Collective, estimator_graphs
-from .common import as_np, resolve_device
-from .irm import check_cells, irm_fit_phases, irm_scores
-from .lasso import _fold_ids
+from ..utils.graphs import Collective
+from .common import as_np
+from .irm import (arm_split_panel, comm_counts, irm_fit_phases, mean_se, phase_scores, run_body,
+                  run_phases)
 
 N_FEATURES_MAX = 32
 N_BINS_MAX = 64
@@ -356,11 +355,6 @@ def eval_sums(psi: torch.Tensor, cost: torch.Tensor, use: torch.Tensor, codes: t
     return torch.stack(out)
 
 
-def _mean_se(s1, s2, n):
-    """mean and SE = sd / sqrt(n) with the n - 1 variance rule of ``irm_finalize``."""
-    return s1 / n, torch.sqrt(((s2 - s1 * s1 / n) / (n - 1) / n).clamp(min=0))
-
-
 def policy_finalize(sums: torch.Tensor, bad: torch.Tensor) -> torch.Tensor:
     """fp64 [2, 20] from the (all-reduced) :func:`eval_sums`: per evaluation set value, SE,
     treat_all, SE, advantage, SE, share treated, n, and per leaf slot (n, mean r, SE). Every
@@ -369,13 +363,13 @@ def policy_finalize(sums: torch.Tensor, bad: torch.Tensor) -> torch.Tensor:
     rows = []
     for u in (0, 1):
         n, s1, s2, p1, p2, npi = (sums[u, k] for k in range(6))
-        v, v_se = _mean_se(p1, p2, n)
-        t, t_se = _mean_se(s1, s2, n)
-        a, a_se = _mean_se(p1 - s1, s2 - p2, n)       # (pi - 1) r: squares (1 - pi) r^2
+        v, v_se = mean_se(p1, p2, n)
+        t, t_se = mean_se(s1, s2, n)
+        a, a_se = mean_se(p1 - s1, s2 - p2, n)        # (pi - 1) r: squares (1 - pi) r^2
         row = [v, v_se, t, t_se, a, a_se, npi / n, n]
         for l in range(4):
             nl, l1, l2 = (sums[u, 6 + 3 * l + k] for k in range(3))
-            row += [nl, *_mean_se(l1, l2, nl)]
+            row += [nl, *mean_se(l1, l2, nl)]
         rows.append(torch.stack(row))
     fin = torch.stack(rows)
     return torch.where(bad > 0, torch.full_like(fin, float("nan")), fin)
@@ -405,9 +399,6 @@ def policy_phases(pan, codes, use, nb, cost, folds: int, depth=2, min_leaf=1, la
     n_rows = int(n_rows) if n_rows is not None else pan.ld
     cost_t = _dev_scalar(cost, torch.float64, pan.device)
 
-    def phase_scores(st):
-        return {**st, "psi": irm_scores(pan, st["coef"], clip, 2)}
-
     def phase_range(st):
         return {**st, "range": score_range(st["psi"], cost_t, use)}
 
@@ -431,7 +422,7 @@ def policy_phases(pan, codes, use, nb, cost, folds: int, depth=2, min_leaf=1, la
             return st
         return Collective(f, capturable=bool(getattr(comm, "capturable", False)))
 
-    phases += [phase_scores, phase_range]
+    phases += [phase_scores(pan, clip), phase_range]
     if reduce is not None:
         phases.append(reduce_max("range"))
     phases.append(phase_hist)
@@ -460,10 +451,8 @@ def irm_policy_panel(pan, codes: torch.Tensor, use: torch.Tensor, nb, cost=0.0, 
     if codes.dim() != 2 or codes.shape[1] != pan.ld or use.numel() != pan.ld:
         raise ValueError(f"codes must be [d, {pan.ld}] and use [{pan.ld}], got "
                          f"{tuple(codes.shape)} and {tuple(use.shape)}")
-    st = None
-    for ph in policy_phases(pan, codes, use, nb, cost, folds, depth, min_leaf, lambda_rule, clip,
-                            comm, seg_counts, n_rows):
-        st = ph(st)
+    st = run_phases(policy_phases(pan, codes, use, nb, cost, folds, depth, min_leaf, lambda_rule,
+                                  clip, comm, seg_counts, n_rows))
     return st["fin"], st["rec"], st["e"], st.get("cv")
 
 
@@ -471,10 +460,10 @@ def _policy_body(pan, codes, use, nb, cost, folds, lambda_rule, clip, depth, min
                  dist=None, counts=None):
     """The whole estimator as one device function (GraphCache captures it):
     (fin [2, 20] fp64, rec | e int64 [17])."""
-    comm = dist.comm if dist is not None else None
+    comm, seg_counts = comm_counts(dist, counts)
     fin, rec, e, _ = irm_policy_panel(pan, codes, use, nb, cost, folds, depth, min_leaf,
                                       lambda_rule, clip, comm=comm, n_rows=n_rows,
-                                      seg_counts=None if counts is None else np.asarray(counts))
+                                      seg_counts=seg_counts)
     return fin, torch.cat([rec, e.to(torch.int64)])
 
 
@@ -499,15 +488,12 @@ def dml_irm_policy_lasso(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0
     graph: as ``dml_irm_lasso``, one captured hipGraph on a GPU; the codes, the use codes, the
     bin counts and the cost are graph inputs, so a call with other features (as many) and
     another cost in the same panel layout replays it."""
-    dev = resolve_device(device)
-    Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
+    Xn = as_np(X)
     check_tree_args(depth, bins, min_leaf)
     feats = check_features(features, Xn.shape[1])
     if not np.isfinite(float(cost)):
         raise ValueError(f"cost must be finite, got {cost}")
-    if not np.isin(Wn, (0.0, 1.0)).all():
-        raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
-    n = len(Yn)
+    n = len(Xn)
     if train is None:
         usen = np.zeros(n, dtype=np.int8)
     else:
@@ -521,19 +507,13 @@ def dml_irm_policy_lasso(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0
     Xf_all = dist.gather_rows(torch.as_tensor(Xf)).numpy() if sharded else Xf
     edges = [feature_edges(Xf_all[:, k], int(bins)) for k in range(len(feats))]
     nb = [len(ed) + 1 for ed in edges]
-    fid = _fold_ids(n, folds, seed, 0, dist)
-    seg = 2 * np.asarray(fid, dtype=np.int64) + Wn.astype(np.int64)
-    counts = np.bincount(seg, minlength=2 * folds).astype(np.float64)
-    ntrain = float((usen == 0).sum())
-    if sharded:
-        t = torch.as_tensor(np.concatenate([counts, [ntrain]])).to(dev)
-        dist.sum_(t)
-        t = t.cpu().numpy()
-        counts, ntrain = t[:2 * folds], float(t[2 * folds])
-    if ntrain < 1:
-        raise ValueError("the train mask leaves no training rows")
-    check_cells(counts, folds)
-    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev)
+    def check_train(ntrain):
+        if ntrain[0] < 1:
+            raise ValueError("the train mask leaves no training rows")
+
+    pan, counts, _, n_total, _ = arm_split_panel(
+        Y, W, X, folds, seed, dtype, device, dist,
+        extra_counts=[(usen == 0).sum()], check_extra=check_train)
     real = pan.row_index >= 0
     cn = np.stack([bin_codes(Xf[:, k], edges[k]) for k in range(len(feats))], axis=1)
     codes = torch.stack([pan.gather_rows(torch.from_numpy(np.ascontiguousarray(cn[:, k])))
@@ -542,15 +522,9 @@ def dml_irm_policy_lasso(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0
                       torch.full((pan.ld,), -1, dtype=torch.int8, device=pan.device))
     nbt = torch.tensor(nb, dtype=torch.int32, device=pan.device)
     cost_t = torch.tensor([float(cost)], dtype=torch.float64, device=pan.device)
-    n_total = dist.n_total if dist is not None else n
-    args = (folds, lambda_rule, float(clip), int(depth), int(min_leaf), int(n_total), dist,
-            tuple(counts.tolist()))
-    g = False
-    if graph and (dist is None or dist.capturable) and pan.data.is_cuda:
-        out, g = estimator_graphs.run("dml_irm_policy", _policy_body,
-                                      (pan, codes, use, nbt, cost_t), *args)
-    else:
-        out = _policy_body(pan, codes, use, nbt, cost_t, *args)
+    out, g = run_body("dml_irm_policy", _policy_body, (pan, codes, use, nbt, cost_t), folds,
+                      lambda_rule, float(clip), int(depth), int(min_leaf), int(n_total), dist,
+                      tuple(counts.tolist()), graph=graph, dist=dist)
     fin = out[0].detach().double().cpu().numpy()
     rec = out[1].detach().cpu().numpy().astype(np.int64)
     return PolicyTreeResult.make(method, rec[:REC], fin, feats, edges, float(cost), int(depth),

@@ -16,7 +16,7 @@ biases, moves theta by at most S k, k = |rho| sqrt(cf_y) sqrt(cf_d / (1 - cf_d))
 theta -/+ S k, their standard errors (from the 3x3 covariance of (psi, b, c)), the robustness
 values and the covariate benchmarks are all functions of 14 fp64 sums over the rows
 (``result.SENS_MOMENTS``): the fit is that of ``irm_phases``, one more instantiation of the
-fused score pass (csrc/irm.hip ``ate_irm_sens_moments``) accumulates them, and everything
+fused score pass (``irm.irm_sens_moments``, csrc/irm.hip) accumulates them, and everything
 after it happens on the host (``result.SensitivityResult``).
 
 A benchmark refits the model without a set of covariates on the same folds. Its Gram is a
@@ -29,77 +29,15 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import _native
 from ..ops.devconst import const
 from ..ops.enet import cv_enet_gaussian
-from ..ops.panel import build_panel, dtype_code
 from ..result import SENS_MOMENTS, SensitivityResult, check_benchmarks, check_scenario
-from ..utils.graphs import estimator_graphs
-from .common import as_np, resolve_device
-from .irm import _yw_columns, check_cells, fit_problems, irm_fit_phases
-from .lasso import _fold_ids, global_seg_counts
+from .common import as_np
+from .irm import (arm_split_panel, comm_counts, fit_problems, irm_fit_phases,  # noqa: F401
+                  irm_sens_moments, run_body, run_phases)
+from .lasso import global_seg_counts
 
 N_SENS = len(SENS_MOMENTS)   # 14
-
-
-def irm_sens_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
-                     nbx: int | None = None) -> torch.Tensor:
-    """The held-out score pass of ``irm.irm_score_moments`` -- same arguments, same dot
-    products, same psi -- accumulating the 14 fp64 moments of the sensitivity analysis
-    (``result.SENS_MOMENTS``). GPU: csrc/irm.hip ``ate_irm_sens_moments`` (``nbx`` blocks per
-    segment; for the same ``nbx`` S psi, S psi^2, n, n_clipped and n_treated carry the bits of
-    ``irm_score_moments``); CPU: the float64 torch twin below, the kernel's oracle."""
-    nseg = pan.nseg
-    nfold = coef.shape[0]
-    if segs_per_fold < 1 or nfold * segs_per_fold < nseg:
-        raise ValueError(f"{nseg} segments at {segs_per_fold} per fold need "
-                         f"{-(-nseg // max(segs_per_fold, 1))} coefficient blocks, got {nfold}")
-    p = len(pan.xcols)
-    if tuple(coef.shape[1:]) != (3, p + 1):
-        raise ValueError(f"coef must be [nfold, 3, {p + 1}], got {tuple(coef.shape)}")
-    y0, y1, w0, w1 = _yw_columns(pan)
-    if not pan.data.is_cuda:
-        X = pan.colmajor().double()
-        c = coef.double()
-        mom = torch.zeros(N_SENS, dtype=torch.float64)
-        lo, hi = clip, 1.0 - clip
-        for s in range(nseg):
-            r0, r1 = (int(v) for v in pan.seg_bounds[s])
-            Xs = X[:, r0:r1]
-            v = Xs[pan.cols["one"]] != 0
-            xs = Xs[pan.xcols][:, v]
-            y = Xs[y0][v] + (Xs[y1][v] if y1 >= 0 else 0.0)
-            w = Xs[w0][v] + (Xs[w1][v] if w1 >= 0 else 0.0)
-            k = s // segs_per_fold
-            g0 = c[k, 0, 0] + c[k, 0, 1:] @ xs
-            g1 = c[k, 1, 0] + c[k, 1, 1:] @ xs
-            m = c[k, 2, 0] + c[k, 2, 1:] @ xs
-            e = m.clamp(lo, hi)
-            psi = g1 - g0 + w * (y - g1) / e - (1.0 - w) * (y - g0) / (1.0 - e)
-            b = torch.where(w != 0, (y - g1) ** 2, (y - g0) ** 2)
-            rr = w / e - (1.0 - w) / (1.0 - e)
-            cc = 2.0 * (1.0 / e + 1.0 / (1.0 - e)) - rr * rr
-            one = torch.ones_like(psi)
-            mom += torch.stack([psi.sum(), (psi * psi).sum(), one.sum(),
-                                ((m < lo) | (m > hi)).double().sum(),
-                                b.sum(), (b * b).sum(), cc.sum(), (cc * cc).sum(),
-                                (psi * b).sum(), (psi * cc).sum(), (b * cc).sum(),
-                                y.sum(), (y * y).sum(), w.sum()])
-        return mom
-    dev = pan.device
-    xc = const(pan.xcols, torch.int32, dev)
-    segs = const(np.asarray(pan.seg_bounds, dtype=np.int64), torch.int64, dev)
-    if nbx is None:
-        nbx = 512 if pan.dtype == torch.bfloat16 else 256      # as irm_score_moments
-    part = torch.empty(nseg * nbx * N_SENS, dtype=torch.float64, device=dev)
-    mom = torch.empty(N_SENS, dtype=torch.float64, device=dev)
-    c = coef.double().contiguous()
-    cs, bs = pan.strides()
-    _native.call("ate_irm_sens_moments", dtype_code(pan.data), pan.data.data_ptr(), cs, bs,
-                 xc.data_ptr(), p, segs.data_ptr(), nseg, segs_per_fold, c.data_ptr(), y0, y1,
-                 w0, w1, pan.cols["one"], float(clip), nbx, part.data_ptr(), mom.data_ptr(),
-                 torch.cuda.current_stream().cuda_stream)
-    return mom
 
 
 def sens_phases(pan, folds: int, lambda_rule="min", clip=0.01, benchmarks=(), comm=None,
@@ -164,18 +102,16 @@ def irm_sens_panel(pan, folds: int, lambda_rule="min", clip=0.01, benchmarks=(),
     model with every covariate; row 1 + j: the model without benchmark set j. Device tensors,
     no host sync (capturable); ``result.SensitivityResult.from_moments`` finishes on the
     host."""
-    st = None
-    for ph in sens_phases(pan, folds, lambda_rule, clip, benchmarks, comm, seg_counts):
-        st = ph(st)
+    st = run_phases(sens_phases(pan, folds, lambda_rule, clip, benchmarks, comm, seg_counts))
     return st["mom"], st.get("cv")
 
 
 def _sens_body(pan, folds, lambda_rule, clip, benchmarks, dist=None, counts=None):
     """The whole call as one device function (GraphCache captures it): the flat moments
     ``cat([long, short_1, ...])``."""
-    comm = dist.comm if dist is not None else None
+    comm, seg_counts = comm_counts(dist, counts)
     mom, _ = irm_sens_panel(pan, folds, lambda_rule, clip, benchmarks, comm=comm,
-                            seg_counts=None if counts is None else np.asarray(counts))
+                            seg_counts=seg_counts)
     return mom.reshape(-1)
 
 
@@ -192,30 +128,13 @@ def dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null
 
     graph: as ``dml_irm_lasso``, one captured hipGraph on a GPU; the benchmark sets are part
     of the cache key. Every further scenario is ``result.bounds(cf_y, cf_d, rho, level)``."""
-    dev = resolve_device(device)
-    Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
     check_scenario(cf_y, cf_d, rho, level)
-    bench = check_benchmarks(benchmarks, Xn.shape[1])
-    if not np.isin(Wn, (0.0, 1.0)).all():
-        raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
-    fid = _fold_ids(len(Yn), folds, seed, 0, dist)
-    seg = 2 * np.asarray(fid, dtype=np.int64) + Wn.astype(np.int64)
-    counts = np.bincount(seg, minlength=2 * folds).astype(np.float64)
-    if dist is not None and dist.world > 1:
-        t = torch.as_tensor(counts).to(dev)
-        dist.sum_(t)
-        counts = t.cpu().numpy()
-    check_cells(counts, folds)
-    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev)
-    args = (folds, lambda_rule, float(clip), bench, dist, tuple(counts.tolist()))
-    g = False
-    if graph and (dist is None or dist.capturable) and pan.data.is_cuda:
-        out, g = estimator_graphs.run("dml_irm_sens", _sens_body, (pan,), *args)
-    else:
-        out = _sens_body(pan, *args)
+    bench = check_benchmarks(benchmarks, as_np(X).shape[1])
+    pan, counts, _, n, _ = arm_split_panel(Y, W, X, folds, seed, dtype, device, dist)
+    out, g = run_body("dml_irm_sens", _sens_body, (pan,), folds, lambda_rule, float(clip), bench,
+                      dist, tuple(counts.tolist()), graph=graph, dist=dist)
     v = out.detach().double().cpu().numpy().reshape(1 + len(bench), N_SENS)
     mom = v[0]
-    n = dist.n_total if dist is not None else len(Yn)
     fin = lambda x: int(round(x)) if np.isfinite(x) else -1
     return SensitivityResult.from_moments(
         method, mom, cf_y, cf_d, rho, level, null,

@@ -12,13 +12,14 @@
 // Pass 1 (ate_cate_moments): n | S psi | S psi^2 | rows per span | v = S b psi | M = S b b'.
 // Pass 2 (ate_cate_boot), with e_i = psi_i - b_i' beta:
 //   Meat = S e^2 b b',   T[r][j] = S xi_i^r e_i b_{i,j}
-// with xi_i^r = +1 / -1 from bit (r % 128) of rand4(seed, P_MULT, r / 128, rid_i), the
-// draws and bit mapping of csrc/gate.hip. Rows with rid < 0 are skipped (padding rows and
-// rows the caller leaves out): they contribute exactly nothing.
+// with the Rademacher multipliers xi_i^r of csrc/boot_common.hpp (the draws, the bit ->
+// replicate mapping, the launch geometry, the bucketing and the slab sum are shared with
+// csrc/gate.hip there). Rows with rid < 0 are skipped (padding rows and rows the caller
+// leaves out): they contribute exactly nothing.
 //
 // Shape (that of gate_boot_kernel): a workgroup of CH threads walks chunks of CH rows
 // (blockIdx.x, grid stride). Per chunk one row per thread is loaded and evaluated, the rows
-// are bucketed by span with a stable counting sort (wave ballots + a [wave][span] table) and
+// are bucketed by span with a stable counting sort (bucket_rows) and
 // a record (b_0..b_3 or e b_0..e b_3, zero above q) per row is written to LDS in bucket order.
 //  - Band sums (count, v, M; Meat): thread t owns function t % 16 of span t / 16 (+ CH / 16 per
 //    pass) -- 1, b_c psi (4), b_a b_c for a <= c (10) -- and walks that span's run with one
@@ -31,14 +32,12 @@
 //    the workgroup's partial slab.
 // No atomics: per-workgroup partials, combined in a fixed order by the sum kernels, so one
 // launch geometry gives one set of bits.
-#include "common.hpp"
+#include "boot_common.hpp"
 
 using namespace ate;
 
 namespace {
 
-constexpr int CHMAX = 256;   // rows per chunk = threads per workgroup (at most)
-constexpr int SPWMAX = 8;    // Philox streams per workgroup (at most): CHMAX / 32
 constexpr int DREG = 8;      // up to this many basis functions: replicate sums in registers
 constexpr int DMAX = 32;     // basis functions (and so spans) at most
 constexpr int QMAX = 3;
@@ -80,54 +79,6 @@ __device__ __forceinline__ int basis_eval_q(int q, const double* sk, int d, doub
     case 2: return basis_eval<2>(sk, d, x, N);
     default: return basis_eval<3>(sk, d, x, N);
   }
-}
-
-// Stable counting sort of a chunk's rows by span: returns this row's position in bucket order
-// (valid rows only) and leaves the run starts in start[0 .. DMAX]. wcnt: [CH / 64][DMAX].
-// Every thread of the workgroup calls it; two barriers inside, the first of which also ends
-// the previous chunk's walks (they read what the caller writes next).
-__device__ __forceinline__ int bucket_rows(bool valid, int g, int (*wcnt)[DMAX], int* start) {
-  const int CH = blockDim.x, nw = CH >> 6;
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-  for (int q = t; q < nw * DMAX; q += CH) (&wcnt[0][0])[q] = 0;
-  uint64_t same = __ballot(valid);
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const uint64_t bk = __ballot(valid && ((g >> k) & 1));
-    same &= ((g >> k) & 1) ? bk : ~bk;
-  }
-  const int rank = __popcll(same & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (valid && rank == 0) wcnt[wid][g] = __popcll(same);
-  __syncthreads();
-  if (t < 64) {             // wave 0: exclusive scan of the span totals, per-wave offsets
-    int tot = 0;
-    if (t < DMAX)
-      for (int w = 0; w < nw; ++w) tot += wcnt[w][t];
-    int inc = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
-    if (t < DMAX) {
-      int off = inc - tot;
-      start[t] = off;
-      if (t == DMAX - 1) start[DMAX] = inc;
-      for (int w = 0; w < nw; ++w) {
-        const int cw = wcnt[w][t];
-        wcnt[w][t] = off;
-        off += cw;
-      }
-    }
-  }
-  __syncthreads();
-  int pos = 0;
-  if (valid) {
-    pos = wcnt[wid][g] + rank;     // stable: rows of a span keep their order
-    ATE_DASSERT(pos >= 0 && pos < CH && pos >= start[g] && pos < start[g + 1]);
-  }
-  return pos;
 }
 
 // the two record entries whose product is band function k: 0 -> 1, 1..4 -> r_c psi,
@@ -205,7 +156,7 @@ __global__ __launch_bounds__(CHMAX) void cate_moments_kernel(
     const int g = basis_eval_q(q, sk, d, valid ? x[i] : sk[0], N);
     m[0] += p;
     m[1] += p * p;
-    const int pos = bucket_rows(valid, g, wcnt, start);
+    const int pos = bucket_rows<DMAX>(valid, g, wcnt, start);
     if (valid) {
 #pragma unroll
       for (int c = 0; c <= QMAX; ++c) rec[pos * REC + c] = N[c];
@@ -360,18 +311,13 @@ __global__ __launch_bounds__(CHMAX) void cate_boot_kernel(
     double e = p;
 #pragma unroll
     for (int cc = 0; cc <= Q; ++cc) e -= N[cc] * sb[g + cc];
-    const int pos = bucket_rows(valid, g, wcnt, start);
+    const int pos = bucket_rows<DMAX>(valid, g, wcnt, start);
     if (valid) {
 #pragma unroll
       for (int cc = 0; cc <= QMAX; ++cc) rec[pos * REC + cc] = e * N[cc];
       rec[pos * REC + 4] = 0.0;
       rec[pos * REC + 5] = 1.0;
-      for (int qq = 0; qq < nsw; ++qq) {
-        if (stream0 + qq < nst) {
-          const u32x4 r = rand4(seed, P_MULT, (uint32_t)(stream0 + qq), (uint64_t)id);
-          sw[pos * nsw + qq] = make_uint4(~r.x, ~r.y, ~r.z, ~r.w);     // inverted: walk_run
-        }
-      }
+      store_words(sw, pos, nsw, stream0, nst, seed, id);
     }
     __syncthreads();
     if (doband) band_accumulate(rec, start, nsp, ia, ic, acc);
@@ -409,44 +355,16 @@ __global__ __launch_bounds__(CHMAX) void cate_boot_kernel(
   if (doband) band_store(PB, nsp, acc);
 }
 
-// T [B][d] from the slabs. A block sums 16 consecutive partial slots: thread (j, sl) adds the
-// workgroups sl, sl + 16, ... of slot j in ascending order and the 16 slices are then added
-// in slice order (fixed order: deterministic for a given launch geometry).
+// T [B][d] from the slabs, by the fixed-order slab_sum.
 __global__ __launch_bounds__(256) void cate_t_sum_kernel(const double* __restrict__ PT, int d,
                                                          int B, int CH, int nbx, int nby,
                                                          double* __restrict__ T) {
-  __shared__ double ra[16][16];
-  const int64_t per = (int64_t)d * 4 * CH;          // a multiple of 16
-  const int j = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int64_t idx = (int64_t)blockIdx.x * 16 + j;
-  const int by = (int)(idx / per);
-  const int64_t rem = idx - by * per;
-  double a = 0.0;
-  if (by < nby)
-#pragma unroll 4
-    for (int bx = sl; bx < nbx; bx += 16) a += PT[((int64_t)by * nbx + bx) * per + rem];
-  ra[sl][j] = a;
-  __syncthreads();
-  if (sl != 0 || by >= nby) return;
-  for (int q = 1; q < 16; ++q) a += ra[q][j];
-  const int t = (int)(rem % CH), k = (int)((rem / CH) & 3), f = (int)(rem / (4 * CH));
-  const int b = (by * (CH >> 5) + (t >> 5)) * 128 + k * 32 + (t & 31);
-  if (b >= B) return;
-  ATE_DASSERT(f < d);
-  T[(int64_t)b * d + f] = a;
+  double a;
+  long long z;
+  int b, f;
+  if (slab_sum<false>(PT, nullptr, d, B, CH, nbx, nby, a, z, b, f)) T[(int64_t)b * d + f] = a;
 }
 
-struct Geo { int nst, CH, nsw, nby; };
-inline Geo geometry(int B) {                         // that of csrc/gate.hip
-  Geo g;
-  g.nst = (B + 127) / 128;
-  const int spw = g.nst < SPWMAX ? g.nst : SPWMAX;
-  g.CH = 64 * ((spw + 1) / 2);
-  g.nsw = g.CH / 32;
-  g.nby = (g.nst + g.nsw - 1) / g.nsw;
-  return g;
-}
-inline int64_t pt_elems(const Geo& g, int d, int nbx) { return (int64_t)g.nby * nbx * d * 4 * g.CH; }
 inline int64_t pb_elems(int nbx) { return (int64_t)nbx * DMAX * NF; }
 constexpr int64_t TOT_ELEMS = DMAX * NF + 2;
 inline bool bad_basis(int d, int q) { return q < 0 || q > QMAX || d < q + 1 || d > DMAX; }
@@ -480,7 +398,7 @@ ATE_KERNEL_SHAPE("cate_boot_kernel<3, slab>", CHMAX, 0, cate_boot_kernel<3, fals
 
 // bytes of the partial workspace of ate_cate_moments(d, q, nbx); -1: bad arguments
 ATE_API int64_t ate_cate_moments_scratch(int d, int q, int nbx) {
-  if (bad_basis(d, q) || nbx < 1 || nbx > 65535) return -1;
+  if (bad_basis(d, q) || bad_boot(1, nbx)) return -1;       // pass 1 has no replicates
   return (pb_elems(nbx) + (int64_t)nbx * 2 + TOT_ELEMS) * 8;
 }
 
@@ -492,8 +410,7 @@ ATE_API int ate_cate_moments(const void* psi, const void* x, const void* rid, in
                              const void* knots, int d, int q, int nbx, void* scratch, void* out,
                              void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (bad_basis(d, q) || nbx < 1 || nbx > 65535) return -1;
-  if (ld < 1 || ld >= ((int64_t)1 << 31)) return -1;
+  if (bad_basis(d, q) || bad_boot(1, nbx, ld)) return -1;
   double* PB = (double*)scratch;
   double* PS = PB + pb_elems(nbx);
   ATE_LAUNCH(cate_moments_kernel, dim3(nbx), dim3(CHMAX), 0, s, (const double*)psi,
@@ -511,8 +428,8 @@ ATE_API int ate_cate_moments(const void* psi, const void* x, const void* rid, in
 
 // bytes of the partial workspace of ate_cate_boot(d, q, B, nbx); -1: bad arguments
 ATE_API int64_t ate_cate_boot_scratch(int d, int q, int B, int nbx) {
-  if (bad_basis(d, q) || B < 1 || B > 4096 || nbx < 1 || nbx > 65535) return -1;
-  return (pt_elems(geometry(B), d, nbx) + pb_elems(nbx) + TOT_ELEMS) * 8;
+  if (bad_basis(d, q) || bad_boot(B, nbx)) return -1;
+  return (slab_elems(geometry(B), d, nbx) + pb_elems(nbx) + TOT_ELEMS) * 8;
 }
 
 // The rows of ate_cate_moments and beta [d] fp64 (device). out [d*d + B*d] fp64: Meat | T.
@@ -521,11 +438,10 @@ ATE_API int ate_cate_boot(const void* psi, const void* x, const void* rid, int64
                           const void* knots, const void* beta, int d, int q, int B, uint64_t seed,
                           int nbx, void* scratch, void* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (bad_basis(d, q) || B < 1 || B > 4096 || nbx < 1 || nbx > 65535) return -1;
-  if (ld < 1 || ld >= ((int64_t)1 << 31)) return -1;
+  if (bad_basis(d, q) || bad_boot(B, nbx, ld)) return -1;
   const Geo g = geometry(B);
   double* PT = (double*)scratch;
-  double* PB = PT + pt_elems(g, d, nbx);
+  double* PB = PT + slab_elems(g, d, nbx);
   const double *p = (const double*)psi, *xx = (const double*)x, *kn = (const double*)knots,
                *be = (const double*)beta;
   const int64_t* r = (const int64_t*)rid;

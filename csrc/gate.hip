@@ -3,15 +3,15 @@
 //
 // For every group g < G and replicate b < B, over the rows i with gid_i = g:
 //   mom[g] = (n_g, S psi_i, S psi_i^2),   A[b][g] = S xi_i^b psi_i,   Z[b][g] = S xi_i^b
-// with xi_i^b = +1 / -1 from bit (b % 128) of rand4(seed, P_MULT, b / 128, rid_i): word
-// (b % 128) / 32, bit b % 32. One Philox call serves 128 replicates of a row and the
-// multipliers never leave registers / LDS. The centred sums of the bootstrap are
-// A - theta_g Z, so no group mean is needed inside the pass.
+// with the Rademacher multipliers xi_i^b of csrc/boot_common.hpp (the draws, the bit ->
+// replicate mapping, the launch geometry, the bucketing and the slab sum are shared with
+// csrc/cate.hip there). The multipliers never leave registers / LDS. The centred sums of the
+// bootstrap are A - theta_g Z, so no group mean is needed inside the pass.
 //
 // Shape: a workgroup of CH = 64..256 threads owns CH / 32 Philox streams (blockIdx.y picks
 // which) and walks chunks of CH rows (blockIdx.x, grid stride). Per chunk: one row per
-// thread is loaded, the rows are bucketed by group with a stable counting sort (wave
-// ballots + a [wave][group] table), and psi plus the rows' Philox words are written to LDS
+// thread is loaded, the rows are bucketed by group with a stable counting sort
+// (bucket_rows), and psi plus the rows' Philox words are written to LDS
 // in bucket order. Thread t then owns bit t % 32 of the four words of stream t / 32 -- four
 // replicates -- and walks each group's run of rows with four fp64 accumulators and four
 // integer bit counts: both LDS reads of a row (psi, the 16-byte word quad) are broadcasts.
@@ -22,14 +22,12 @@
 // stream block: lane g of each wave collects group g's rows from the wave's 64 lanes
 // (readlane, row order). No atomics: per-workgroup partials, combined in a fixed order by
 // gate_sum_kernel, so one launch geometry gives one set of bits.
-#include "common.hpp"
+#include "boot_common.hpp"
 
 using namespace ate;
 
 namespace {
 
-constexpr int CHMAX = 256;   // rows per chunk = threads per workgroup (at most)
-constexpr int SPWMAX = 8;    // Philox streams per workgroup (at most): CHMAX / 32
 constexpr int GREG = 8;      // up to this many groups: accumulators in registers
 constexpr int GMAX = 64;
 
@@ -118,47 +116,10 @@ __global__ __launch_bounds__(CHMAX) void gate_boot_kernel(
     }
     const int64_t id = valid ? rid[i] : 0;
     ATE_DASSERT(id >= 0);
-    for (int q = t; q < nw * GMAX; q += CH) (&wcnt[0][0])[q] = 0;
-    // lanes of this wave holding the same group, by ballots over the 6 bits of g
-    uint64_t same = __ballot(valid);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const uint64_t bk = __ballot(valid && ((g >> k) & 1));
-      same &= ((g >> k) & 1) ? bk : ~bk;
-    }
-    const int rank = __popcll(same & ((1ull << lane) - 1ull));
-    __syncthreads();          // table zeroed; every thread has left the previous chunk's walk
-    if (valid && rank == 0) wcnt[wid][g] = __popcll(same);
-    __syncthreads();
-    if (t < GMAX) {           // wave 0: exclusive scan of the group totals, per-wave offsets
-      int tot = 0;
-      for (int w = 0; w < nw; ++w) tot += wcnt[w][t];
-      int inc = tot;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-      }
-      int off = inc - tot;
-      start[t] = off;
-      if (t == GMAX - 1) start[GMAX] = inc;
-      for (int w = 0; w < nw; ++w) {
-        const int cw = wcnt[w][t];
-        wcnt[w][t] = off;
-        off += cw;
-      }
-    }
-    __syncthreads();
+    const int pos = bucket_rows<GMAX>(valid, g, wcnt, start);
     if (valid) {
-      const int pos = wcnt[wid][g] + rank;   // stable: rows of a group keep their order
-      ATE_DASSERT(pos >= 0 && pos < CH && pos < start[g + 1]);
       sp[pos] = p;
-      for (int q = 0; q < nsw; ++q) {
-        if (stream0 + q < nst) {
-          const u32x4 r = rand4(seed, P_MULT, (uint32_t)(stream0 + q), (uint64_t)id);
-          sw[pos * nsw + q] = make_uint4(~r.x, ~r.y, ~r.z, ~r.w);     // inverted: walk_run
-        }
-      }
+      store_words(sw, pos, nsw, stream0, nst, seed, id);
     }
     __syncthreads();
     if (active) {
@@ -204,57 +165,23 @@ __global__ __launch_bounds__(CHMAX) void gate_boot_kernel(
   }
 }
 
-// out = mom [G][3] | A [B][G] | Z [B][G]. A block sums 16 consecutive partial slots: thread
-// (j, sl) adds the workgroups sl, sl + 16, ... of slot j in ascending order and the 16 slices
-// are then added in slice order (fixed order: deterministic for a given launch geometry).
+// out = mom [G][3] | A [B][G] | Z [B][G]: the group moments of the workgroups in ascending
+// order, A and Z by the fixed-order slab_sum.
 __global__ __launch_bounds__(256) void gate_sum_kernel(
     const double* __restrict__ PA, const int* __restrict__ PZ, const double* __restrict__ PM,
     int G, int B, int CH, int nbx, int nby, double* __restrict__ out) {
-  __shared__ double ra[16][16];
-  __shared__ long long rz[16][16];
-  const int64_t per = (int64_t)G * 4 * CH;          // a multiple of 16
-  const int j = threadIdx.x & 15, sl = threadIdx.x >> 4;
   if (blockIdx.x == 0 && threadIdx.x < G * 3) {
     double v = 0.0;
     for (int bx = 0; bx < nbx; ++bx) v += PM[(int64_t)bx * G * 3 + threadIdx.x];
     out[threadIdx.x] = v;
   }
-  const int64_t idx = (int64_t)blockIdx.x * 16 + j;
-  const int by = (int)(idx / per);
-  const int64_t rem = idx - by * per;
-  double a = 0.0;
-  long long z = 0;
-  if (by < nby)
-#pragma unroll 4
-    for (int bx = sl; bx < nbx; bx += 16) {
-      const int64_t o = ((int64_t)by * nbx + bx) * per + rem;
-      a += PA[o];
-      z += PZ[o];
-    }
-  ra[sl][j] = a;
-  rz[sl][j] = z;
-  __syncthreads();
-  if (sl != 0 || by >= nby) return;
-  for (int q = 1; q < 16; ++q) { a += ra[q][j]; z += rz[q][j]; }
-  const int t = (int)(rem % CH), k = (int)((rem / CH) & 3), g = (int)(rem / (4 * CH));
-  const int b = (by * (CH >> 5) + (t >> 5)) * 128 + k * 32 + (t & 31);
-  if (b >= B) return;
-  ATE_DASSERT(g < G);
+  double a;
+  long long z;
+  int b, g;
+  if (!slab_sum<true>(PA, PZ, G, B, CH, nbx, nby, a, z, b, g)) return;
   out[(int64_t)G * 3 + (int64_t)b * G + g] = a;
   out[(int64_t)G * 3 + (int64_t)B * G + (int64_t)b * G + g] = (double)z;
 }
-
-struct Geo { int nst, CH, nsw, nby; };
-inline Geo geometry(int B) {
-  Geo q;
-  q.nst = (B + 127) / 128;
-  const int spw = q.nst < SPWMAX ? q.nst : SPWMAX;
-  q.CH = 64 * ((spw + 1) / 2);
-  q.nsw = q.CH / 32;
-  q.nby = (q.nst + q.nsw - 1) / q.nsw;
-  return q;
-}
-inline int64_t pa_elems(const Geo& q, int G, int nbx) { return (int64_t)q.nby * nbx * G * 4 * q.CH; }
 
 }  // namespace
 
@@ -263,9 +190,8 @@ ATE_KERNEL_SHAPE("gate_boot_kernel<slab>", CHMAX, 0, gate_boot_kernel<false>)
 
 // bytes of the partial workspace of ate_group_boot(G, B, nbx); -1: bad arguments
 ATE_API int64_t ate_group_boot_scratch(int G, int B, int nbx) {
-  if (G < 1 || G > GMAX || B < 1 || B > 4096 || nbx < 1) return -1;
-  const Geo q = geometry(B);
-  return pa_elems(q, G, nbx) * 12 + (int64_t)nbx * G * 3 * 8;
+  if (G < 1 || G > GMAX || bad_boot(B, nbx)) return -1;
+  return slab_elems(geometry(B), G, nbx) * 12 + (int64_t)nbx * G * 3 * 8;
 }
 
 // psi [ld] fp64, gid [ld] int32 (group in [0, G), -1: skip the row), rid [ld] int64 global
@@ -275,10 +201,9 @@ ATE_API int ate_group_boot(const void* psi, const void* gid, const void* rid, in
                            int B, uint64_t seed, int nbx, void* scratch, void* out,
                            void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (G < 1 || G > GMAX || B < 1 || B > 4096 || nbx < 1 || nbx > 65535) return -1;
-  if (ld < 1 || ld >= ((int64_t)1 << 31)) return -1;    // per-workgroup integer counts
+  if (G < 1 || G > GMAX || bad_boot(B, nbx, ld)) return -1;
   const Geo q = geometry(B);
-  const int64_t na = pa_elems(q, G, nbx);
+  const int64_t na = slab_elems(q, G, nbx);
   double* PA = (double*)scratch;
   double* PM = PA + na;
   int* PZ = (int*)(PM + (int64_t)nbx * G * 3);
