@@ -99,6 +99,8 @@ _SIGS = {
     "ate_dml_resid_moments": "ipllpipipiiiiiippp",
     "ate_dml_resid_exact": "pllpipipiiiiiiippp",
     "ate_irm_score_moments": "ipllpipiipiiiiidippp",
+    "ate_irm_score_moments_multi": "ipllpipiipipiiiiiidippp",
+    "ate_irm_score_multi_smax": "",
     "ate_irm_scores": "ipllpipiipiiiiidipp",
     "ate_irm_sens_moments": "ipllpipiipiiiiidippp",
     "ate_group_boot": "pppliiuippp",

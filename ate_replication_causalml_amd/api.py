@@ -239,13 +239,26 @@ def ate_dml(Y, W, X, folds=5, lambda_rule="min", method="DML cross-fit (LASSO)",
 
 
 def ate_dml_irm(Y, W, X, folds=5, lambda_rule="min", clip=0.01,
-                method="DML-IRM cross-fit (LASSO)", run=None) -> AteResult:
+                method="DML-IRM cross-fit (LASSO)", run=None, repeats=1,
+                aggregate="median") -> AteResult:
     """K-fold cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1)
     with CV-LASSO nuisances: per-arm outcome regressions and the linear-probability
     propensity (clipped to [clip, 1 - clip]) on the fold Gram stack; the ATE under
-    heterogeneous effects, doubly robust (estimators/irm.py). W must be binary."""
+    heterogeneous effects, doubly robust (estimators/irm.py). W must be binary.
+    ``repeats`` > 1: repeated cross-fitting over that many K-fold partitions (at most
+    ``folds``), ``aggregate`` "median" (default) or "mean", as ate_dml; the partitions share
+    one Gram pass and one fused score pass (estimators/irm.irm_repeated_phases)."""
     run = _run(run)
-    with trace("ate_dml_irm", folds=folds):
+    with trace("ate_dml_irm", folds=folds, repeats=repeats):
+        if repeats != 1:
+            if _ref(run):
+                from .reference import estimators as R
+                return R.dml_irm_lasso_repeated(Y, W, X, folds, repeats, run.seed, lambda_rule,
+                                                clip, aggregate)
+            from .estimators import irm as DI
+            return DI.dml_irm_lasso_repeated(Y, W, X, folds, repeats, run.seed, lambda_rule,
+                                             clip, aggregate, device=run.device(),
+                                             dtype=run.dtype)
         if _ref(run):
             from .reference import estimators as R
             return R.dml_irm_lasso(Y, W, X, folds=folds, seed=run.seed, lambda_rule=lambda_rule,

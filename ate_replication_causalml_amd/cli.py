@@ -45,7 +45,25 @@ def _dml(a):
         # interactive model: arm-split panel (segment 2k + a = fold k, W = a), AIPW score
         from .estimators.irm import irm_crossfit_panel
         if a.repeats > 1:
-            raise SystemExit("--model irm has no repeated cross-fitting")
+            # repeated cross-fitting: 2 K*K micro-arm segments, `repeats` K-fold partitions
+            if (a.gate_col is not None or a.cate_col is not None or a.policy_cols is not None
+                    or a.sensitivity):
+                raise SystemExit("--repeats applies to the ATE only: not with --gate-col, "
+                                 "--cate-col, --policy-cols or --sensitivity")
+            from .estimators.irm import irm_repeated_panel
+            pan = synthetic_panel(a.n, p=a.p, folds=a.folds * a.folds, seed=a.seed,
+                                  dtype=a.dtype, device=dev, arm_split=True)
+            try:
+                res, splits, mom = irm_repeated_panel(pan, a.folds, a.repeats, a.lambda_rule,
+                                                      a.clip, aggregate=a.aggregate)
+            except ValueError as e:
+                raise SystemExit(str(e))
+            r = read_result(res, "DML-IRM cross-fit (LASSO, repeated)", n=a.n)
+            print(json.dumps({"ate": r.ate, "se": r.se, "lower_ci": r.lower_ci,
+                              "upper_ci": r.upper_ci, "repeats": a.repeats,
+                              "aggregate": a.aggregate, "splits": splits.cpu().tolist(),
+                              "n_clipped": [int(round(v)) for v in mom[:, 3].cpu().tolist()]}))
+            return 0
         pan = synthetic_panel(a.n, p=a.p, folds=a.folds, seed=a.seed, dtype=a.dtype, device=dev,
                               arm_split=True)
         if a.gate_col is not None and a.sensitivity:

@@ -16,6 +16,10 @@ their pairwise sums. All 3 K (K + 1) path problems (3 nuisances x K outer folds 
 K - 1 inner CV)) run in ONE ``ate_enet_path`` launch (``ops/enet.cv_enet_gaussian(full_y=)``),
 and one fused pass over the panel (csrc/irm.hip) accumulates the 8 score moments.
 
+Repeated cross-fitting (:func:`dml_irm_lasso_repeated`, :func:`irm_repeated_phases`): S
+partitions built from K*K micro-groups on a 2 K*K-segment panel share one Gram pass and one
+multi-split score pass (:func:`irm_score_moments_multi`), median-aggregated.
+
 The estimators on the same score (gate, cate, policy, sensitivity) share what lives here: the
 score pass in its three forms (:func:`irm_score_moments`, :func:`irm_sens_moments`,
 :func:`irm_scores` -- one CPU twin ``_score_terms``, one launcher ``_score_launch``), the
@@ -30,13 +34,15 @@ import torch
 
 from .. import _native
 from ..ops.devconst import const
-from ..ops.enet import cv_enet_gaussian
+from ..ops.enet import (MAX_PATH_PROBLEMS, cv_enet_gaussian, cv_problem_count,
+                        default_lambda_min_ratio)
 from ..ops.gram import gram
 from ..ops.panel import build_panel, dtype_code
 from ..result import SENS_MOMENTS, AteResult
 from ..utils.graphs import estimator_graphs
 from .common import as_np, resolve_device
-from .lasso import _fold_ids, _tri_index, allreduce_sym_, global_seg_counts
+from .lasso import (_fold_ids, _tri_index, allreduce_sym_, global_seg_counts, median_aggregate,
+                    micro_fold_map)
 
 N_MOMENTS = 8   # [S psi, S psi^2, n, n_clipped, S w(y-g1)^2, S (1-w)(y-g0)^2, S (w-m)^2, n_treated]
 
@@ -62,11 +68,14 @@ def _score_args(pan, coef, segs_per_fold):
     return p
 
 
-def _score_terms(pan, coef, segs_per_fold):
+def _score_terms(pan, coef, segs_per_fold, blk=None):
     """The float64 CPU twin of the score pass (the kernels' oracle): per segment
     ``(r0, r1, v, y, w, g0, g1, m)`` -- its row range, the mask of its real rows, and over
-    those rows the targets, the two outcome regressions and the unclipped propensity."""
-    _score_args(pan, coef, segs_per_fold)
+    those rows the targets, the two outcome regressions and the unclipped propensity.
+    blk [S, ngroups] (the multi-split pass): segment group g uses block ``blk[t][g]`` under
+    split t, and g0, g1, m are lists of S tensors, each the expression of the single pass."""
+    if blk is None:
+        _score_args(pan, coef, segs_per_fold)
     y0, y1, w0, w1 = _yw_columns(pan)
     X = pan.colmajor().double()
     c = coef.double()
@@ -78,6 +87,11 @@ def _score_terms(pan, coef, segs_per_fold):
         y = Xs[y0][v] + (Xs[y1][v] if y1 >= 0 else 0.0)
         w = Xs[w0][v] + (Xs[w1][v] if w1 >= 0 else 0.0)
         k = s // segs_per_fold
+        if blk is not None:
+            ks = [int(b[k]) for b in blk]
+            yield (r0, r1, v, y, w, *([c[q, r, 0] + c[q, r, 1:] @ xs for q in ks]
+                                      for r in range(3)))
+            continue
         yield (r0, r1, v, y, w, c[k, 0, 0] + c[k, 0, 1:] @ xs, c[k, 1, 0] + c[k, 1, 1:] @ xs,
                c[k, 2, 0] + c[k, 2, 1:] @ xs)
 
@@ -87,11 +101,13 @@ def aipw_psi(y, w, g0, g1, e):
     return g1 - g0 + w * (y - g1) / e - (1.0 - w) * (y - g0) / (1.0 - e)
 
 
-def _score_launch(name, pan, coef, clip, segs_per_fold, nbx, n_out, moments):
+def _score_launch(name, pan, coef, clip, segs_per_fold, nbx, n_out, moments, blk=None):
     """One instantiation of the fused score pass (csrc/irm.hip entry point ``name``) with
     ``nbx`` blocks per segment. ``moments``: the entry point sums ``n_out`` moments (a
-    ``partial`` workspace, then the result); otherwise it writes ``n_out`` = ld row scores."""
-    p = _score_args(pan, coef, segs_per_fold)
+    ``partial`` workspace, then the result); otherwise it writes ``n_out`` = ld row scores.
+    blk [S, ngroups] (checked by the caller): the multi-split entry point, whose arguments
+    add (nblk, blk, S) after ``coef``; ``n_out`` = S * 8 then."""
+    p = len(pan.xcols) if blk is not None else _score_args(pan, coef, segs_per_fold)
     y0, y1, w0, w1 = _yw_columns(pan)
     dev = pan.device
     xc = const(pan.xcols, torch.int32, dev)
@@ -104,9 +120,11 @@ def _score_launch(name, pan, coef, clip, segs_per_fold, nbx, n_out, moments):
     if moments:
         bufs = (torch.empty(pan.nseg * nbx * n_out, dtype=torch.float64, device=dev), out)
     c = coef.double().contiguous()
+    split = () if blk is None else (coef.shape[0], const(blk, torch.int32, dev).data_ptr(),
+                                    blk.shape[0])
     cs, bs = pan.strides()
     _native.call(name, dtype_code(pan.data), pan.data.data_ptr(), cs, bs, xc.data_ptr(), p,
-                 segs.data_ptr(), pan.nseg, segs_per_fold, c.data_ptr(), y0, y1, w0, w1,
+                 segs.data_ptr(), pan.nseg, segs_per_fold, c.data_ptr(), *split, y0, y1, w0, w1,
                  pan.cols["one"], float(clip), nbx, *(b.data_ptr() for b in bufs),
                  torch.cuda.current_stream().cuda_stream)
     return out
@@ -124,15 +142,59 @@ def irm_score_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold
         return _score_launch("ate_irm_score_moments", pan, coef, clip, segs_per_fold, nbx,
                              N_MOMENTS, True)
     mom = torch.zeros(N_MOMENTS, dtype=torch.float64)
-    lo, hi = clip, 1.0 - clip
     for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
-        psi = aipw_psi(y, w, g0, g1, m.clamp(lo, hi))
-        one = torch.ones_like(psi)
-        mom += torch.stack([psi.sum(), (psi * psi).sum(), one.sum(),
-                            ((m < lo) | (m > hi)).double().sum(),
-                            (w * (y - g1) ** 2).sum(), ((1.0 - w) * (y - g0) ** 2).sum(),
-                            ((w - m) ** 2).sum(), w.sum()])
+        mom += _segment_moments(y, w, g0, g1, m, clip)
     return mom
+
+
+def _segment_moments(y, w, g0, g1, m, clip):
+    """The 8 moments (N_MOMENTS) of one segment's rows in the float64 twin."""
+    lo, hi = clip, 1.0 - clip
+    psi = aipw_psi(y, w, g0, g1, m.clamp(lo, hi))
+    one = torch.ones_like(psi)
+    return torch.stack([psi.sum(), (psi * psi).sum(), one.sum(),
+                        ((m < lo) | (m > hi)).double().sum(),
+                        (w * (y - g1) ** 2).sum(), ((1.0 - w) * (y - g0) ** 2).sum(),
+                        ((w - m) ** 2).sum(), w.sum()])
+
+
+def score_multi_smax() -> int:
+    """The most splits one pass of the multi-split score kernel serves (csrc/irm.hip)."""
+    return int(_native.hip().ate_irm_score_multi_smax())
+
+
+def irm_score_moments_multi(pan, coef: torch.Tensor, blk, clip: float = 0.01,
+                            segs_per_fold: int = 2, nbx: int | None = None) -> torch.Tensor:
+    """The pass of :func:`irm_score_moments` for S partitions of the same segments at once
+    (repeated cross-fitting) -> [S, 8] fp64 moments.
+
+    coef: [nblk, 3, p+1] fp64; blk: host integers [S, ngroups], ngroups = ceil(nseg /
+    segs_per_fold): under split t, segment s uses block ``blk[t][s // segs_per_fold]``. Row t
+    of the result carries the bits of ``irm_score_moments(pan, coef[blk[t]], ...)`` at the
+    same ``nbx``. GPU: csrc/irm.hip ``ate_irm_score_moments_multi`` -- every column of the
+    union of the splits' supports is read once for all splits, ``one``, Y and W once per row;
+    the panel is read again only past :func:`score_multi_smax` splits. CPU: the float64 torch
+    twin, one loop over the segments with S scores per row."""
+    blk = np.ascontiguousarray(np.asarray(blk.cpu() if torch.is_tensor(blk) else blk),
+                               dtype=np.int64)
+    p = len(pan.xcols)
+    ngroups = -(-pan.nseg // max(segs_per_fold, 1))
+    if segs_per_fold < 1 or blk.ndim != 2 or blk.shape[0] < 1 or blk.shape[1] != ngroups:
+        raise ValueError(f"blk must be [S, {ngroups}] ({pan.nseg} segments at {segs_per_fold} "
+                         f"per group), got {tuple(blk.shape)}")
+    if coef.dim() != 3 or tuple(coef.shape[1:]) != (3, p + 1):
+        raise ValueError(f"coef must be [nblk, 3, {p + 1}], got {tuple(coef.shape)}")
+    nblk, S = coef.shape[0], blk.shape[0]
+    if blk.min() < 0 or blk.max() >= nblk:
+        raise ValueError(f"blk entries must be coefficient blocks in [0, {nblk})")
+    if not pan.data.is_cuda:
+        mom = torch.zeros((S, N_MOMENTS), dtype=torch.float64)
+        for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold, blk):
+            for t in range(S):
+                mom[t] += _segment_moments(y, w, g0[t], g1[t], m[t], clip)
+        return mom
+    return _score_launch("ate_irm_score_moments_multi", pan, coef, clip, segs_per_fold, nbx,
+                         S * N_MOMENTS, True, blk).view(S, N_MOMENTS)
 
 
 def irm_sens_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
@@ -247,11 +309,43 @@ def fit_problems(pan, K: int, counts):
     return counts3, full_sets, full_y, [pan.cols["Y"], pan.cols["W"]]
 
 
+def gram_phases(pan, comm=None):
+    """The head of every IRM phase list: the per-segment Gram stack (K01: tile kernel, slab
+    reduce; state "G") and, at world > 1, its symmetric all-reduce over row shards (C01).
+    Returns (phases, reduce): ``reduce(name)`` makes an all-reduce phase of a state tensor
+    (None at world 1)."""
+    from ..utils.graphs import Collective
+    dist = comm is not None and comm.world_size > 1
+
+    def phase_gram(_):
+        return {"G": gram(pan, stage="tiles")}
+
+    def phase_gram_reduce(st):
+        return {"G": gram(pan, stage="reduce", out=st["G"])}
+
+    cap = bool(getattr(comm, "capturable", False))
+
+    def reduce(name):
+        def f(st):
+            comm.all_reduce_(st[name])
+            return st
+        return Collective(f, capturable=cap)     # RCCL: captured inside the step's graph
+
+    phases = [phase_gram, phase_gram_reduce]
+    if dist:
+        _tri_index(pan.P, pan.device)            # built here, never inside a capture
+
+        def reduce_g(st):
+            allreduce_sym_(comm, st["G"])
+            return st
+        phases.append(Collective(reduce_g, capturable=cap))
+    return phases, (reduce if dist else None)
+
+
 def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None):
     """The phases of :func:`irm_phases` up to the fitted coefficients (A, C01, B; state "G",
     "cv", "coef"), shared with the group-effect estimator (estimators/gate.py), and the
     factory ``reduce(name)`` of an all-reduce phase of a state tensor (None at world 1)."""
-    from ..utils.graphs import Collective
     dist = comm is not None and comm.world_size > 1
     K = folds
     if seg_counts is None:
@@ -262,12 +356,6 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
         raise ValueError(f"DML-IRM needs {2 * K} segments, this shard's panel has {pan.nseg}")
     counts3, full_sets, full_y, ycols = fit_problems(pan, K, counts)
 
-    def phase_gram(_):
-        return {"G": gram(pan, stage="tiles")}
-
-    def phase_gram_reduce(st):
-        return {"G": gram(pan, stage="reduce", out=st["G"])}
-
     def phase_fit(st):
         G = st["G"]
         G3 = torch.cat([G, G[0::2] + G[1::2]])
@@ -276,27 +364,9 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
         coef = (cv.coef_min if lambda_rule == "min" else cv.coef_1se).reshape(K, 3, -1)
         return {**st, "cv": cv, "coef": coef.double().contiguous()}
 
-    cap = bool(getattr(comm, "capturable", False))
-
-    def reduce(name):
-        def f(st):
-            comm.all_reduce_(st[name])
-            return st
-        return Collective(f, capturable=cap)     # RCCL: captured inside the step's graph
-
-    def reduce_sym(name):
-        _tri_index(pan.P, pan.device)            # built here, never inside a capture
-
-        def f(st):
-            allreduce_sym_(comm, st[name])
-            return st
-        return Collective(f, capturable=cap)
-
-    phases = [phase_gram, phase_gram_reduce]
-    if dist:
-        phases.append(reduce_sym("G"))
+    phases, reduce = gram_phases(pan, comm)
     phases.append(phase_fit)
-    return phases, (reduce if dist else None)
+    return phases, reduce
 
 
 def phase_scores(pan, clip):
@@ -329,9 +399,144 @@ def irm_crossfit_panel(pan, folds: int, lambda_rule="min", clip=0.01, comm=None,
     return st["res"], st["mom"], st.get("cv")
 
 
+# ---------------------------------------------------------------- repeated cross-fitting
+def check_partition_cells(counts, folds: int, repeats: int):
+    """The sibling of :func:`check_cells` for the micro layout (segment 2m + a = micro-group
+    m, arm a; K*K micro-groups): every (fold, arm) cell of every used partition
+    (``lasso.micro_fold_map``) needs a row. A micro-group with an empty arm is legal."""
+    K = folds
+    c = np.asarray(counts, dtype=np.float64)
+    if len(c) != 2 * K * K:
+        raise ValueError(f"repeated DML-IRM needs 2*K*K = {2 * K * K} segments (micro-group m, "
+                         f"arm a -> 2m + a), the panel has {len(c)}")
+    for s in range(repeats):
+        fold = micro_fold_map(K, s)
+        for a in (0, 1):
+            cell = np.bincount(fold, weights=c[a::2], minlength=K)
+            for k in np.flatnonzero(cell <= 0):
+                raise ValueError(f"empty (fold, arm) cell in partition {s}: fold {int(k)}, "
+                                 f"arm W={a} has no rows")
+
+
+def _path_launches(ratios, cap):
+    """Consecutive partitions grouped into as few path launches as possible: at most ``cap``
+    partitions per launch, evenly filled, and only partitions with the same lambda ratio
+    share one (``cv_enet_gaussian`` picks one ratio per launch: a partition keeps the ratio,
+    and so the bits, of its own solve). Returns [(first, last + 1), ...]."""
+    out, s, S = [], 0, len(ratios)
+    while s < S:
+        e = s
+        while e < S and ratios[e] == ratios[s]:
+            e += 1
+        n = e - s
+        nl = -(-n // cap)
+        for i in range(nl):
+            out.append((s + i * n // nl, s + (i + 1) * n // nl))
+        s = e
+    return out
+
+
+def irm_repeated_phases(pan, folds: int, repeats: int, lambda_rule="min", clip=0.01, comm=None,
+                        seg_counts=None, aggregate="median"):
+    """Repeated K-fold cross-fitting of DML-IRM (Chernozhukov et al. 2018 §3.4): ``repeats``
+    = S partitions of the rows, one cross-fitted AIPW fit per partition, median-aggregated
+    (``lasso.median_aggregate``). The panel holds 2*K*K segments, segment 2m + a = micro-group
+    m, arm a; partition s puts micro-group m = K a' + b in fold (a' + s b) mod K
+    (``lasso.micro_fold_map``). As for ``ate_dml(repeats=)`` the partitions are built from ONE
+    assignment to K*K micro-groups, so they are correlated (two partitions share one
+    micro-group per fold pair), and there are at most K of them: 1 <= repeats <= K. Phases
+    (utils.graphs.SegmentedStep captures them, one graph at world 1):
+
+    A  the 2 K*K micro-arm Gram stack (K01): tile kernel, slab reduce, ONCE   device
+    C01 symmetric all-reduce of the stack over row shards                     collective
+    B  per partition the 2K fold-arm Grams (a 0/1 matrix times the stack, fp64) and their K
+       arm sums: the 3K-segment stack of :func:`fit_problems`; all partitions' problems in
+       as few path launches as ``ate_enet_path`` admits (256 co-resident problems), each
+       holding whole partitions with segment ids offset per partition                device
+    B' ONE fused score pass for all S partitions (csrc/irm.hip
+       ``ate_irm_score_moments_multi``), blk[s][m] = s K + fold of m under s        device
+    C06 one all-reduce of the [S, 8] moments                                   collective
+    C  theta / SE per split, the aggregate                                      device
+
+    A partition's coefficients carry the bits of solving that partition alone: its problems
+    name only its own 3K segments. The result state holds "res" [2] (the aggregate), "splits"
+    [S, 2], "mom" [S, 8] and "coef" [S K, 3, p+1]. Raises ValueError, before any device work,
+    when one partition alone exceeds the path launch (large K)."""
+    K, Sn = folds, repeats
+    if pan.nseg != 2 * K * K:
+        raise ValueError(f"repeated DML-IRM needs 2*K*K = {2 * K * K} micro-arm segments, the "
+                         f"panel has {pan.nseg}")
+    if not 1 <= Sn <= K:
+        raise ValueError(f"repeats must be in 1..{K} (distinct partitions of K*K micro-groups)")
+    dist = comm is not None and comm.world_size > 1
+    if seg_counts is None:
+        seg_counts = global_seg_counts(pan, comm) if dist else np.asarray(pan.seg_nreal)
+    counts = np.asarray(seg_counts, dtype=np.float64)
+    check_partition_cells(counts, K, Sn)
+    dev, P, p = pan.device, pan.P, len(pan.xcols)
+    maps = [micro_fold_map(K, s) for s in range(Sn)]
+    # partition s: fold-arm segment 2k + a = the sum of the micro-arm segments 2m + a, m in k
+    M = np.zeros((Sn, 2 * K, 2 * K * K))
+    for s, fold in enumerate(maps):
+        for a in (0, 1):
+            M[s, 2 * fold + a, 2 * np.arange(K * K) + a] = 1.0
+    cell_counts = M @ counts                                              # [Sn, 2K]
+    probs = [fit_problems(pan, K, cc) for cc in cell_counts]             # per partition
+    _, sets1, full_y1, ycols = probs[0]
+    per = cv_problem_count(3 * K, sets1, len(ycols), full_y1)
+    if per > MAX_PATH_PROBLEMS:
+        raise ValueError(f"one partition of K = {K} folds is {per} path problems, more than "
+                         f"the {MAX_PATH_PROBLEMS} one path launch holds")
+    Mall = const(M.reshape(Sn * 2 * K, 2 * K * K), torch.float64, dev)
+    # the lambda ratio cv_enet_gaussian picks for the partition alone
+    ratios = [default_lambda_min_ratio(min(c3[list(fs)].sum() for fs in sets1), p)
+              for c3, *_ in probs]
+    launches = _path_launches(ratios, MAX_PATH_PROBLEMS // per)
+    blk = np.stack([s * K + maps[s] for s in range(Sn)])                 # [Sn, K*K]
+
+    def phase_fit(st):
+        Gfa = (Mall @ st["G"].view(2 * K * K, P * P)).view(Sn, 2 * K, P, P)
+        G3 = torch.cat([Gfa, Gfa[:, 0::2] + Gfa[:, 1::2]], 1)           # [Sn, 3K, P, P]
+        coefs = []
+        for s0, s1 in launches:
+            n = s1 - s0
+            cv = cv_enet_gaussian(
+                G3[s0:s1].reshape(n * 3 * K, P, P), pan, pan.xcols, ycols,
+                full_sets=[[i * 3 * K + q for q in fs] for i in range(n) for fs in sets1],
+                seg_counts=np.concatenate([probs[s][0] for s in range(s0, s1)]),
+                full_y=full_y1 * n, lambda_min_ratio=ratios[s0])
+            coefs.append((cv.coef_min if lambda_rule == "min" else cv.coef_1se)
+                         .reshape(n * K, 3, -1))
+        return {**st, "coef": torch.cat(coefs).double().contiguous()}
+
+    def phase_score(st):
+        return {**st, "mom": irm_score_moments_multi(pan, st["coef"], blk, clip, 2)}
+
+    def phase_final(st):
+        res = torch.stack([irm_finalize(st["mom"][s]) for s in range(Sn)])
+        return {**st, "splits": res, "res": median_aggregate(res[:, 0], res[:, 1], aggregate)}
+
+    phases, reduce = gram_phases(pan, comm)
+    phases += [phase_fit, phase_score]
+    if reduce is not None:
+        phases.append(reduce("mom"))
+    phases.append(phase_final)
+    return phases
+
+
+def irm_repeated_panel(pan, folds: int, repeats: int, lambda_rule="min", clip=0.01, comm=None,
+                       seg_counts=None, aggregate="median"):
+    """Eager run of :func:`irm_repeated_phases` on a micro-arm panel (from host arrays
+    ``build_panel(folds=2 * micro + W)``, at scale ``synthetic_panel(folds=K * K,
+    arm_split=True)``): (aggregate [2], splits [S, 2], mom [S, 8])."""
+    st = run_phases(irm_repeated_phases(pan, folds, repeats, lambda_rule, clip, comm,
+                                        seg_counts, aggregate))
+    return st["res"], st["splits"], st["mom"]
+
+
 # ---------------------------------------------------------------- the shared front end
 def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts=None,
-                    check_extra=None):
+                    check_extra=None, cells=check_cells):
     """The prologue of every ``dml_irm_*`` estimator: the binary-W check, the fold ids, the
     (global) rows per (fold, arm) cell and the arm-split panel (segment 2k + a = fold k,
     W = a) on ``device``. Returns (pan, counts [2K], extra, n_total, rid).
@@ -339,7 +544,9 @@ def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts
     extra_counts: further local counts of the caller (rows per group, per span, ...). Over
     row shards they are summed in the one all-reduce that sums the cell counts, come back as
     ``extra`` and are handed to ``check_extra`` before the panel is built. rid: the rows'
-    global ids in panel row order (the key of the bootstrap multipliers), -1 on padding."""
+    global ids in panel row order (the key of the bootstrap multipliers), -1 on padding.
+    cells: the check of the cell counts, ``cells(counts, folds)`` (repeated cross-fitting
+    passes its own: its K*K micro-groups may have an empty arm)."""
     dev = resolve_device(device)
     Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
     if not np.isin(Wn, (0.0, 1.0)).all():
@@ -355,8 +562,8 @@ def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts
         counts, extra = t[:2 * folds], None if extra is None else t[2 * folds:]
     if check_extra is not None:
         check_extra(extra)
-    check_cells(counts, folds)
-    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev)
+    cells(counts, folds)
+    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev, nseg=2 * folds)
     rid = torch.where(pan.row_index >= 0,
                       pan.row_index + (dist.row_offset if dist is not None else 0),
                       torch.full_like(pan.row_index, -1))
@@ -411,3 +618,44 @@ def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
                 rmse_g1=float(np.sqrt(mom[4] / nt)), rmse_m=float(np.sqrt(mom[6] / mom[2])),
                 hipgraph=g)
     return AteResult.make(method, v[0], v[1], **diag)
+
+
+def _irm_repeated_body(pan, folds, repeats, lambda_rule, clip, aggregate, dist=None,
+                       counts=None):
+    """The whole repeated cross-fit as one device function: [res, splits, mom] flattened."""
+    comm, seg_counts = comm_counts(dist, counts)
+    res, splits, mom = irm_repeated_panel(pan, folds, repeats, lambda_rule, clip, comm,
+                                          seg_counts, aggregate)
+    return torch.cat([res, splits.reshape(-1), mom.reshape(-1)])
+
+
+def dml_irm_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="min",
+                           clip=0.01, aggregate="median",
+                           method="DML-IRM cross-fit (LASSO, repeated)", device=None,
+                           dtype="f64", dist=None, graph=True):
+    """``repeats`` = S K-fold cross-fitted AIPW fits on S partitions of the rows, aggregated
+    by the median rule (:func:`irm_repeated_phases`; "mean": the means). Rows go to K*K
+    micro-groups by the balanced Philox assignment of ``dml_plr_lasso_repeated`` (stream 0);
+    partition s is ``micro_fold_map(K, s)``, so 1 <= repeats <= K and the partitions are
+    correlated. One Gram pass and one fused score pass serve all partitions; on a GPU the
+    call is one captured hipGraph. Matches reference.estimators.dml_irm_lasso_repeated.
+    diagnostics: n, repeats, aggregate, splits (the S (ATE, SE) pairs), n_clipped per split,
+    n_treated, hipgraph."""
+    K = folds
+    if not 1 <= repeats <= K:
+        raise ValueError(f"repeats must be in 1..{K} (distinct partitions of K*K micro-groups)")
+    pan, counts, _, n, _ = arm_split_panel(
+        Y, W, X, K * K, seed, dtype, device, dist,
+        cells=lambda c, _: check_partition_cells(c, K, repeats))
+    out, g = run_body("dml_irm_repeated", _irm_repeated_body, (pan,), K, repeats, lambda_rule,
+                      float(clip), aggregate, dist, tuple(counts.tolist()), graph=graph,
+                      dist=dist)
+    v = out.detach().double().cpu().numpy()
+    splits = v[2:2 + 2 * repeats].reshape(repeats, 2)
+    mom = v[2 + 2 * repeats:].reshape(repeats, N_MOMENTS)
+
+    def count(x):
+        return int(round(x)) if np.isfinite(x) else -1
+    return AteResult.make(method, v[0], v[1], n=n, repeats=repeats, aggregate=aggregate,
+                          splits=splits.tolist(), n_clipped=[count(x) for x in mom[:, 3]],
+                          n_treated=count(mom[0, 7]), hipgraph=g)

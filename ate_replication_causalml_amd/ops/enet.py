@@ -77,22 +77,10 @@ def _rescale_vp(vp, p):
     return vp * p / vp.sum()
 
 
-def cv_enet_gaussian(G: torch.Tensor, panel, xcols, ycols, full_sets=None, penalty_factor=None,
-                     alpha=1.0, nlambda=100, lambda_min_ratio=None, thresh=1e-7,
-                     maxit=100000, seg_counts=None, full_y=None) -> EnetCvResult:
-    """Cross-validated gaussian elastic net from the segment Gram stack ``G`` [nseg,P,P].
-
-    full_sets: list of lists of segment ids (default: one set with all segments).
-    seg_counts: rows per segment (default: the panel's; pass the GLOBAL counts when G
-    was all-reduced over row shards). Problems are ordered (full set f, y index).
-    full_y: one index into ``ycols`` per full set: full set f is then solved for that
-    target only (one problem per full set, e.g. per-arm outcome and propensity nuisances
-    in one launch); default: every full set for every target. The target statistics of a
-    (training set, y) pair no problem names are computed but never read (a zero-variance
-    target there gets scale 1, csrc/enet.hip enet_prep_stats_kernel / _cv_cpu)."""
-    nseg = G.shape[0]
-    P = G.shape[1]
-    p = len(xcols)
+def _cv_tables(nseg, full_sets, ycols, nreal, nlambda, full_y):
+    """The training sets and problem tables of :func:`cv_enet_gaussian`: (full_sets, masks
+    [ntrain, nseg], full_keys, full_probs, fold_probs, fold_ycol, fold_holds, fold_index,
+    nfold). The path launch solves ``len(full_probs) + len(fold_probs)`` problems."""
     ny = len(ycols)
     if full_sets is None:
         full_sets = [list(range(nseg))]
@@ -117,12 +105,6 @@ def cv_enet_gaussian(G: torch.Tensor, panel, xcols, ycols, full_sets=None, penal
     masks = np.zeros((len(tsets), nseg), dtype=np.uint8)
     for i, ts in enumerate(tsets):
         masks[i, list(ts)] = 1
-    nreal = np.asarray(panel.seg_nreal if seg_counts is None else seg_counts, dtype=np.float64)
-    n_full = [nreal[list(fs)].sum() for fs in full_sets]
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 1e-4 if min(n_full) > p else 1e-2
-    vp = _rescale_vp(penalty_factor, p)
-    L = nlambda
     if full_y is None:
         ys_of = [list(range(ny))] * len(full_sets)
     else:
@@ -155,6 +137,52 @@ def cv_enet_gaussian(G: torch.Tensor, panel, xcols, ycols, full_sets=None, penal
     fold_ycol = [fold_ycol[i] for i in perm]
     fold_holds = [fold_holds[i] for i in perm]
     fold_index = inv[fold_index].astype(np.int32)
+    return (full_sets, masks, full_keys, full_probs, fold_probs, fold_ycol, fold_holds,
+            fold_index, nfold)
+
+
+def cv_problem_count(nseg, full_sets=None, ny=1, full_y=None) -> int:
+    """Path problems (full-data + CV folds) of a :func:`cv_enet_gaussian` call with these
+    full sets, counted from its own tables. ``ate_enet_path`` keeps every problem of a launch
+    co-resident and refuses more than :data:`MAX_PATH_PROBLEMS` (status -3)."""
+    t = _cv_tables(nseg, full_sets, list(range(ny)), np.ones(nseg), 1, full_y)
+    return len(t[3]) + len(t[4])
+
+
+MAX_PATH_PROBLEMS = 256   # csrc/enet.hip ate_enet_path
+
+
+def default_lambda_min_ratio(n_train_min, p) -> float:
+    """glmnet's lambda.min.ratio for a launch whose smallest full training set has
+    ``n_train_min`` rows: 1e-4 with more rows than covariates, else 1e-2."""
+    return 1e-4 if n_train_min > p else 1e-2
+
+
+def cv_enet_gaussian(G: torch.Tensor, panel, xcols, ycols, full_sets=None, penalty_factor=None,
+                     alpha=1.0, nlambda=100, lambda_min_ratio=None, thresh=1e-7,
+                     maxit=100000, seg_counts=None, full_y=None) -> EnetCvResult:
+    """Cross-validated gaussian elastic net from the segment Gram stack ``G`` [nseg,P,P].
+
+    full_sets: list of lists of segment ids (default: one set with all segments).
+    seg_counts: rows per segment (default: the panel's; pass the GLOBAL counts when G
+    was all-reduced over row shards). Problems are ordered (full set f, y index).
+    full_y: one index into ``ycols`` per full set: full set f is then solved for that
+    target only (one problem per full set, e.g. per-arm outcome and propensity nuisances
+    in one launch); default: every full set for every target. The target statistics of a
+    (training set, y) pair no problem names are computed but never read (a zero-variance
+    target there gets scale 1, csrc/enet.hip enet_prep_stats_kernel / _cv_cpu)."""
+    nseg = G.shape[0]
+    P = G.shape[1]
+    p = len(xcols)
+    ny = len(ycols)
+    nreal = np.asarray(panel.seg_nreal if seg_counts is None else seg_counts, dtype=np.float64)
+    (full_sets, masks, full_keys, full_probs, fold_probs, fold_ycol, fold_holds, fold_index,
+     nfold) = _cv_tables(nseg, full_sets, ycols, nreal, nlambda, full_y)
+    n_full = [nreal[list(fs)].sum() for fs in full_sets]
+    if lambda_min_ratio is None:
+        lambda_min_ratio = default_lambda_min_ratio(min(n_full), p)
+    vp = _rescale_vp(penalty_factor, p)
+    L = nlambda
     if G.is_cuda:
         return _cv_gpu(G, P, nseg, masks, xcols, ycols, p, ny, vp, panel.cols["one"], full_probs,
                        fold_probs, fold_ycol, fold_holds, fold_index, nfold, alpha,

@@ -126,10 +126,12 @@ def _round_up(x, m):
 
 
 def build_panel(X, W=None, Y=None, folds=None, dtype="f64", device="cpu", extra_cols=(),
-                col_align=None, split_hi_lo=None) -> DevicePanel:
+                col_align=None, split_hi_lo=None, nseg=None) -> DevicePanel:
     """Assemble a panel from host arrays.
 
     folds: optional (n,) int fold id -> one padded segment per fold (in fold order).
+    nseg: at least this many segments (default: the largest fold id + 1), so that a layout
+    keeps its trailing segments when no row falls in them (they hold padding rows only).
     extra_cols: names of zero-initialised scratch columns to reserve.
     X may be a torch tensor (e.g. already in HBM): its fold gather and transposition
     then run on ``device`` (no host round trip of the n x p block); same values.
@@ -165,7 +167,7 @@ def build_panel(X, W=None, Y=None, folds=None, dtype="f64", device="cpu", extra_
     if folds is None:
         folds = np.zeros(n, dtype=np.int64)
     folds = np.asarray(folds, dtype=np.int64)
-    K = int(folds.max()) + 1 if n else 1
+    K = max(int(folds.max()) + 1 if n else 1, int(nseg or 0))
     order = np.argsort(folds, kind="stable")
     counts = np.bincount(folds, minlength=K)
     padded = np.array([_round_up(max(c, 1), ROW_ALIGN) for c in counts])

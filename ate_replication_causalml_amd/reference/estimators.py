@@ -841,6 +841,35 @@ def dml_plr_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="
                           n=len(Y), repeats=repeats, splits=np.stack([th, se], 1).tolist())
 
 
+def dml_irm_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="min", clip=0.01,
+                           aggregate="median", method="DML-IRM cross-fit (LASSO, repeated)"):
+    """Repeated cross-fitting of the interactive model: S = repeats calls of the row-by-row
+    dml_irm_lasso on the partitions of dml_plr_lasso_repeated (K*K micro-groups, partition s
+    puts group m = K a + b in fold (a + s b) mod K), aggregated in the same way."""
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    if not 1 <= repeats <= folds:
+        raise ValueError(f"repeats must be in 1..{folds} (distinct partitions of K*K micro-groups)")
+    micro = rng.fold_ids(len(Y), folds * folds, seed, stream=0)
+    a, b = np.divmod(micro, folds)
+    rs = []
+    for s in range(repeats):
+        try:
+            rs.append(dml_irm_lasso(Y, W, X, folds, seed, lambda_rule, clip, method,
+                                    fold_ids=(a + s * b) % folds))
+        except ValueError as e:
+            if "empty (fold, arm) cell" not in str(e):
+                raise
+            raise ValueError(str(e).replace("cell:", f"cell in partition {s}:")) from None
+    th, se = np.array([r.ate for r in rs]), np.array([r.se for r in rs])
+    agg = np.median if aggregate == "median" else np.mean
+    t = float(agg(th))
+    return AteResult.make(method, t, float(np.sqrt(agg(se * se + (th - t) ** 2))), n=len(Y),
+                          repeats=repeats, aggregate=aggregate,
+                          splits=np.stack([th, se], 1).tolist(),
+                          n_clipped=[r.diagnostics["n_clipped"] for r in rs],
+                          n_treated=rs[0].diagnostics["n_treated"])
+
+
 def dml_from_residuals(yr, wr, method):
     """Orthogonal-score combine: theta = sum(wr yr)/sum(wr^2); SE from the
     Neyman score psi = (yr - theta wr) wr, J = mean(wr^2)."""

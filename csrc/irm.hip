@@ -351,6 +351,321 @@ int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols
   return 0;
 }
 
+// ---------------------------------------------------------------- S partitions, one pass
+// Repeated cross-fitting scores every row under S partitions of the same segments: split t
+// gives segment group g = s / segs_per_fold the coefficient block blk[t][g]. The kernels
+// below run NSP splits in one pass over the panel: the 3 NSP coefficient vectors of the
+// segment are staged in LDS, interleaved per column (cv[j * 3 NSP + 3 t + r]: one column's
+// coefficients are one contiguous LDS read), the ordered union of their supports is
+// compacted, every column of that union is read ONCE for all splits, and `one`, Y and W are
+// read once per row. Every per-row accumulator is a register indexed at compile time (NSP is
+// a template parameter, the loops over splits are unrolled).
+//
+// Shared bits: for every split t the moments carry the bits of ate_irm_score_moments called
+// with that split's coefficient blocks at the same nbx. A thread owns the same rows, visits
+// the columns in the same ascending-j order, and a column outside split t's own support has
+// the coefficient 0 there: fma(0, x, acc) = acc for every finite x, so the wider union leaves
+// each dot product as it was (but for an accumulator that is exactly -0.0, which becomes +0.0:
+// the score adds, subtracts and compares it, so no moment changes). After the dot products the row goes through the same
+// irm_accumulate, the block through the same block_sum<8>, and the partials of one split
+// through the same fixed-order sum (irm_sum_multi_kernel: thread i sums blocks i, i + 256,
+// ... of its split, then block_sum<8>).
+constexpr int IRM_SMAX = 4;   // splits per pass: 0 bytes of scratch and >= 2 waves / SIMD for
+                              // every instantiation (profiles/irm_repeated/README.md)
+
+// compact_support3 for NV interleaved vectors: cv[(1 + j) * NV + v], xc[j]; column j stays
+// when any of its NV coefficients is nonzero. The whole block must call it.
+template <int NV, typename C>
+__device__ int compact_support_n(C* cv, int* xc, int p, int* wcnt /* [>= 16] */) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  int base = 0;
+  for (int j0 = 0; j0 < p; j0 += blockDim.x) {
+    const int j = j0 + threadIdx.x;
+    C val[NV];
+    bool keep = false;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      val[v] = j < p ? cv[(int64_t)(1 + j) * NV + v] : C(0);
+      keep = keep || val[v] != C(0);
+    }
+    const int c = j < p ? xc[j] : 0;
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) wcnt[wid] = __popcll(m);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wid; ++w) off += wcnt[w];
+    int tot = base;
+    for (int w = 0; w < nw; ++w) tot += wcnt[w];
+    const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();                                      // all reads of the dense slots done
+    ATE_DASSERT(pos <= j);                                // compaction only moves entries down
+    if (keep) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) cv[(int64_t)(1 + pos) * NV + v] = val[v];
+      xc[pos] = c;
+    }
+    __syncthreads();
+    base = tot;
+  }
+  return base;
+}
+
+// stage the 3 NSP coefficient vectors of segment group g (splits s0 .. s0 + NSP - 1) and the
+// column list; returns the size of the compacted union
+template <int NSP, typename C>
+__device__ __forceinline__ int stage_multi(C* cv, int* xc, const int* __restrict__ xcols, int p,
+                                           int P, const double* __restrict__ coef, int nblk,
+                                           const int* __restrict__ blk, int ngroups, int g, int s0,
+                                           int* wcnt) {
+  ATE_DASSERT(g >= 0 && g < ngroups && nblk >= 1);
+  for (int j = threadIdx.x; j < p; j += blockDim.x) {
+    xc[j] = xcols[j];
+    ATE_DASSERT(xc[j] >= 0 && (P == 0 || xc[j] < P));
+  }
+#pragma unroll
+  for (int t = 0; t < NSP; ++t) {
+    const int k = blk[(int64_t)(s0 + t) * ngroups + g];
+    ATE_DASSERT(k >= 0 && k < nblk);
+    for (int j = threadIdx.x; j <= p; j += blockDim.x)
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+        cv[(int64_t)j * (3 * NSP) + 3 * t + r] = (C)coef[((int64_t)k * 3 + r) * (p + 1) + j];
+  }
+  __syncthreads();
+  return compact_support_n<3 * NSP>(cv, xc, p, wcnt);
+}
+
+template <int NSP>
+__device__ __forceinline__ void write_partial_multi(double (&v)[NSP][NM], double* red,
+                                                    double* partial, int s0, int nsplit) {
+  double* out = partial + (((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nsplit + s0) * NM;
+#pragma unroll
+  for (int t = 0; t < NSP; ++t) {
+    block_sum<NM>(v[t], red);
+    if (threadIdx.x == 0)
+#pragma unroll
+      for (int q = 0; q < NM; ++q) out[t * NM + q] = v[t][q];
+  }
+}
+
+// fp32 / fp64 column-major panels: irm_score_kernel<T, RPT, MOMENTS> for NSP splits at once.
+// partial: [nseg * nbx][nsplit][8], this pass writes splits s0 .. s0 + NSP - 1.
+template <typename T, int RPT, int NSP>
+__global__ __launch_bounds__(256) void irm_score_multi_kernel(
+    const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p, int P,
+    const Seg* __restrict__ segs, int nseg, int spf, const double* __restrict__ coef, int nblk,
+    const int* __restrict__ blk /*[nsplit][ngroups]*/, int ngroups, int s0, int nsplit, int y0,
+    int y1, int w0, int w1, int vcol, double clip, double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  constexpr int NV = 3 * NSP;
+  double* cv = sh;                                // [p+1][NV]
+  int* xc = (int*)(sh + (int64_t)NV * (p + 1));   // [p]
+  __shared__ double red[16 * NM];
+  __shared__ int wcnt[16];
+  const int s = blockIdx.y;
+  ATE_DASSERT(s < nseg && spf >= 1 && y0 >= 0 && w0 >= 0 && vcol >= 0);
+  ATE_DASSERT(P == 0 || (y0 < P && w0 < P && vcol < P && y1 < P && w1 < P));
+  ATE_DASSERT(s0 >= 0 && s0 + NSP <= nsplit);
+  p = stage_multi<NSP>(cv, xc, xcols, p, P, coef, nblk, blk, ngroups, s / spf, s0, wcnt);
+  const Seg sg = segs[s];
+  ATE_DASSERT(sg.r0 >= 0 && sg.r0 <= sg.r1 && sg.r1 <= ld);
+  double v[NSP][NM] = {};
+  for (int64_t base = sg.r0 + (int64_t)blockIdx.x * 256 * RPT; base < sg.r1;
+       base += (int64_t)gridDim.x * 256 * RPT) {
+    double a[NSP][3][RPT];
+    int64_t ii[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      ii[r] = base + r * 256 + threadIdx.x;
+#pragma unroll
+      for (int t = 0; t < NSP; ++t) {
+        a[t][0][r] = cv[3 * t];
+        a[t][1][r] = cv[3 * t + 1];
+        a[t][2][r] = cv[3 * t + 2];
+      }
+    }
+    for (int j = 0; j < p; ++j) {
+      const double* cj = cv + (int64_t)(1 + j) * NV;
+      const int c = xc[j];
+      double x[RPT];
+#pragma unroll
+      for (int r = 0; r < RPT; ++r) x[r] = ii[r] < sg.r1 ? ld_col(X, ld, c, ii[r]) : 0.0;
+#pragma unroll
+      for (int t = 0; t < NSP; ++t) {
+        const double b0 = cj[3 * t], b1 = cj[3 * t + 1], bm = cj[3 * t + 2];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+          a[t][0][r] += b0 * x[r];
+          a[t][1][r] += b1 * x[r];
+          a[t][2][r] += bm * x[r];
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      if (ii[r] >= sg.r1) continue;
+      if (ld_col(X, ld, vcol, ii[r]) == 0.0) continue;          // padding row
+      const double y = ld_col(X, ld, y0, ii[r]) + (y1 >= 0 ? ld_col(X, ld, y1, ii[r]) : 0.0);
+      const double w = ld_col(X, ld, w0, ii[r]) + (w1 >= 0 ? ld_col(X, ld, w1, ii[r]) : 0.0);
+      ATE_DASSERT(spf != 2 || w == (double)(s & 1));
+#pragma unroll
+      for (int t = 0; t < NSP; ++t)
+        irm_accumulate(v[t], y, w, a[t][0][r], a[t][1][r], a[t][2][r], clip);
+    }
+  }
+  write_partial_multi<NSP>(v, red, partial, s0, nsplit);
+}
+
+// bf16 panels (column-major and 64-row blocked): irm_score_bf16_kernel<MOMENTS> for NSP splits
+// at once -- 8 consecutive rows per thread, fp32 dot products, the score in fp64.
+template <int NSP>
+__global__ __launch_bounds__(256) void irm_score_multi_bf16_kernel(
+    const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
+    int P, int64_t ld, const Seg* __restrict__ segs, int nseg, int spf,
+    const double* __restrict__ coef, int nblk, const int* __restrict__ blk, int ngroups, int s0,
+    int nsplit, int y0, int y1, int w0, int w1, int vcol, double clip,
+    double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) float shf[];
+  constexpr int NV = 3 * NSP;
+  float* cv = shf;                                 // [p+1][NV]
+  int* xc = (int*)(shf + (int64_t)NV * (p + 1));   // [p]
+  __shared__ double red[16 * NM];
+  __shared__ int wcnt[16];
+  const int s = blockIdx.y;
+  ATE_DASSERT(s < nseg && spf >= 1 && y0 >= 0 && w0 >= 0 && vcol >= 0);
+  ATE_DASSERT(P == 0 || (y0 < P && w0 < P && vcol < P && y1 < P && w1 < P));
+  ATE_DASSERT(s0 >= 0 && s0 + NSP <= nsplit);
+  p = stage_multi<NSP>(cv, xc, xcols, p, P, coef, nblk, blk, ngroups, s / spf, s0, wcnt);
+  const Seg sg = segs[s];
+  ATE_DASSERT(sg.r0 >= 0 && sg.r0 <= sg.r1 && (ld == 0 || sg.r1 <= ld) && (sg.r0 & 7) == 0 &&
+              (sg.r1 & 7) == 0);
+  auto ld8 = [&](int c, int64_t i, float (&o)[8]) {
+    ATE_DASSERT((i & 7) == 0 && c >= 0 && (P == 0 || c < P) && (ld == 0 || i + 8 <= ld));
+    // (c, i) at c*cs + (i/64)*bs + i%64; the 8 rows never straddle a block (i % 8 == 0)
+    const uint4 u = *reinterpret_cast<const uint4*>(X + (int64_t)c * cs + (i >> 6) * bs + (i & 63));
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      o[2 * q] = __uint_as_float(w[q] << 16);
+      o[2 * q + 1] = __uint_as_float(w[q] & 0xFFFF0000u);
+    }
+  };
+  double v[NSP][NM] = {};
+  for (int64_t i = sg.r0 + ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < sg.r1;
+       i += (int64_t)gridDim.x * 256 * 8) {
+    float a[NSP][3][8];
+#pragma unroll
+    for (int t = 0; t < NSP; ++t)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        a[t][0][r] = cv[3 * t];
+        a[t][1][r] = cv[3 * t + 1];
+        a[t][2][r] = cv[3 * t + 2];
+      }
+    // 4 splits hold 160 accumulator registers: no second column in flight there
+#pragma clang loop unroll_count(NSP >= 4 ? 1 : 2)
+    for (int j = 0; j < p; ++j) {
+      float x[8];
+      ld8(xc[j], i, x);
+      const float* cj = cv + (int64_t)(1 + j) * NV;
+#pragma unroll
+      for (int t = 0; t < NSP; ++t) {
+        const float b0 = cj[3 * t], b1 = cj[3 * t + 1], bm = cj[3 * t + 2];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          a[t][0][r] += b0 * x[r];
+          a[t][1][r] += b1 * x[r];
+          a[t][2][r] += bm * x[r];
+        }
+      }
+    }
+    float vv[8], ya[8], yb[8], wa[8], wb[8];
+    ld8(vcol, i, vv);
+    ld8(y0, i, ya);
+    ld8(w0, i, wa);
+    if (y1 >= 0) ld8(y1, i, yb); else { for (int r = 0; r < 8; ++r) yb[r] = 0.f; }
+    if (w1 >= 0) ld8(w1, i, wb); else { for (int r = 0; r < 8; ++r) wb[r] = 0.f; }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      if (vv[r] == 0.f) continue;                                 // padding row
+      const double y = (double)ya[r] + (double)yb[r];
+      const double w = (double)wa[r] + (double)wb[r];
+      ATE_DASSERT(spf != 2 || w == (double)(s & 1));
+#pragma unroll
+      for (int t = 0; t < NSP; ++t)
+        irm_accumulate(v[t], y, w, (double)a[t][0][r], (double)a[t][1][r], (double)a[t][2][r],
+                       clip);
+    }
+  }
+  write_partial_multi<NSP>(v, red, partial, s0, nsplit);
+}
+
+// irm_sum_kernel<8> per split: block t sums partial[b][t][:] over b in the order of the
+// single-split reduction (thread i: b = i, i + 256, ...; then block_sum<8>).
+__global__ __launch_bounds__(256) void irm_sum_multi_kernel(const double* __restrict__ partial,
+                                                            int nb, int nsplit,
+                                                            double* __restrict__ out) {
+  __shared__ double red[16 * NM];
+  const int t = blockIdx.x;
+  ATE_DASSERT(t < nsplit);
+  double v[NM] = {};
+  for (int b = threadIdx.x; b < nb; b += 256)
+#pragma unroll
+    for (int q = 0; q < NM; ++q) v[q] += partial[((int64_t)b * nsplit + t) * NM + q];
+  block_sum<NM>(v, red);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int q = 0; q < NM; ++q) out[(int64_t)t * NM + q] = v[q];
+}
+
+struct MultiArgs {
+  int dtype;
+  const void* X;
+  int64_t cs, bs;
+  const void* xcols;
+  int p;
+  const void* segs;
+  int nseg, spf;
+  const void* coef;
+  int nblk;
+  const void* blk;
+  int ngroups, nsplit, y0, y1, w0, w1, vcol;
+  double clip;
+  int nbx;
+  void* partial;
+};
+
+inline size_t multi_lds(int dtype, int p, int nsp) {
+  const size_t esz = dtype == 3 ? sizeof(float) : sizeof(double);
+  return (size_t)3 * nsp * (p + 1) * esz + (size_t)p * sizeof(int);
+}
+
+// one pass: splits s0 .. s0 + NSP - 1
+template <int NSP>
+int irm_multi_pass(const MultiArgs& a, int s0, hipStream_t s) {
+  const int64_t ld = a.bs == 64 ? a.cs : 0;
+  const int P = a.bs == 64 ? 0 : (int)(a.bs / 64);
+  const size_t sh = multi_lds(a.dtype, a.p, NSP);
+  const dim3 grid(a.nbx, a.nseg), block(256);
+  if (a.dtype == 1)
+    ATE_LAUNCH((irm_score_multi_kernel<float, 4, NSP>), grid, block, sh, s, (const float*)a.X, a.cs,
+               (const int*)a.xcols, a.p, P, (const Seg*)a.segs, a.nseg, a.spf,
+               (const double*)a.coef, a.nblk, (const int*)a.blk, a.ngroups, s0, a.nsplit, a.y0,
+               a.y1, a.w0, a.w1, a.vcol, a.clip, (double*)a.partial);
+  else if (a.dtype == 2)
+    ATE_LAUNCH((irm_score_multi_kernel<double, 4, NSP>), grid, block, sh, s, (const double*)a.X,
+               a.cs, (const int*)a.xcols, a.p, P, (const Seg*)a.segs, a.nseg, a.spf,
+               (const double*)a.coef, a.nblk, (const int*)a.blk, a.ngroups, s0, a.nsplit, a.y0,
+               a.y1, a.w0, a.w1, a.vcol, a.clip, (double*)a.partial);
+  else
+    ATE_LAUNCH(irm_score_multi_bf16_kernel<NSP>, grid, block, sh, s, (const bf16_t*)a.X, a.cs,
+               a.bs, (const int*)a.xcols, a.p, P, ld, (const Seg*)a.segs, a.nseg, a.spf,
+               (const double*)a.coef, a.nblk, (const int*)a.blk, a.ngroups, s0, a.nsplit, a.y0,
+               a.y1, a.w0, a.w1, a.vcol, a.clip, (double*)a.partial);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 // dtype 1 f32, 2 f64, 3 bf16. (cs, bs): element (c, i) at c*cs + (i/64)*bs + i%64 (fp32 /
@@ -399,6 +714,54 @@ ATE_API int ate_irm_sens_moments(int dtype, const void* X, int64_t cs, int64_t b
   if (rc != 0) return rc;
   ATE_LAUNCH(irm_sum_kernel<NS>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
              (double*)moments);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The most splits one pass of ate_irm_score_moments_multi serves.
+ATE_API int ate_irm_score_multi_smax() { return IRM_SMAX; }
+
+// The pass of ate_irm_score_moments for nsplit partitions of the same segments at once
+// (repeated cross-fitting). coef: [nblk][3][p+1] fp64; blk: int32 [nsplit][ngroups] on the
+// device, ngroups = ceil(nseg / segs_per_fold) -- segment group g uses block blk[t][g] under
+// split t (every entry in [0, nblk): the caller checks them, the debug build asserts it).
+// partial: [nseg*nbx][nsplit][8]; moments: [nsplit][8]. moments[t] carries the bits of
+// ate_irm_score_moments with coef gathered by blk[t] at the same nbx (see the kernels). The
+// panel is read ceil(nsplit / n) times, n = the most splits per pass: IRM_SMAX, or fewer
+// when 3 n coefficient vectors would not fit the LDS bound of the single-split pass.
+ATE_API int ate_irm_score_moments_multi(int dtype, const void* X, int64_t cs, int64_t bs,
+                                        const void* xcols, int p, const void* segs, int nseg,
+                                        int segs_per_fold, const void* coef, int nblk,
+                                        const void* blk, int nsplit, int y0, int y1, int w0,
+                                        int w1, int vcol, double clip, int nbx, void* partial,
+                                        void* moments, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype < 1 || dtype > 3 || (dtype != 3 && bs != 64)) return -1;
+  if (p < 0 || nseg < 1 || nseg > 65535 || segs_per_fold < 1 || nbx < 1 || cs < 64 || bs < 64)
+    return -1;
+  if (y0 < 0 || w0 < 0 || vcol < 0) return -1;
+  if (nblk < 1 || nsplit < 1 || nsplit > 65535 || blk == nullptr || coef == nullptr) return -1;
+  if (!(clip >= 0.0 && clip < 0.5)) return -1;
+  int per = IRM_SMAX;                        // dynamic + static LDS within the 64 KB default
+  while (per > 1 && multi_lds(dtype, p, per) > 64 * 1024 - 2048) --per;
+  if (multi_lds(dtype, p, per) > 64 * 1024 - 2048) return -1;
+  const MultiArgs a{dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, nblk, blk,
+                    (nseg + segs_per_fold - 1) / segs_per_fold, nsplit, y0, y1, w0, w1, vcol,
+                    clip, nbx, partial};
+  static_assert(IRM_SMAX == 4, "one case per instantiation below");
+  for (int s0 = 0; s0 < nsplit; s0 += per) {
+    const int n = nsplit - s0 < per ? nsplit - s0 : per;
+    int rc = -1;
+    switch (n) {
+      case 1: rc = irm_multi_pass<1>(a, s0, s); break;
+      case 2: rc = irm_multi_pass<2>(a, s0, s); break;
+      case 3: rc = irm_multi_pass<3>(a, s0, s); break;
+      case 4: rc = irm_multi_pass<4>(a, s0, s); break;
+    }
+    if (rc != 0) return rc;
+  }
+  ATE_LAUNCH(irm_sum_multi_kernel, dim3(nsplit), dim3(256), 0, s, (const double*)partial,
+             nbx * nseg, nsplit, (double*)moments);
   ATE_CHECK_LAUNCH();
   return 0;
 }

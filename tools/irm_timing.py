@@ -8,7 +8,15 @@ one process and timed with device events. Recorded, not gated: profiles/irm/READ
 ``--score-only``: a few eager launches of the fused score pass alone after one fit, for a
 separate ``rocprofv3 --kernel-trace --stats -- python tools/irm_timing.py --score-only``
 run; the JSON line carries the bytes the pass reads, rows x (union support + 5 columns) x 2
-summed over the folds, to turn the kernel's time into bytes/s."""
+summed over the folds, to turn the kernel's time into bytes/s.
+
+``--repeats S``: repeated cross-fitting (``irm_repeated_phases`` on the 2 K*K micro-arm panel)
+beside what a user without it must do, S single-partition calls of ``irm_phases`` on the
+same rows: one captured repeated call and S captured single calls, alternated. With
+``--score-only``: after one repeated fit, the fused multi-split score pass
+(``irm_score_multi*`` kernels) and S launches of ``ate_irm_score_moments`` on the same panel
+and coefficients, for the kernel trace; the JSON line carries each side's unique bytes.
+Recorded in profiles/irm_repeated/README.md."""
 import argparse
 import json
 import os
@@ -31,6 +39,7 @@ def main():
     ap.add_argument("--calls", type=int, default=20, help="timed calls of each estimator")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--score-only", action="store_true")
+    ap.add_argument("--repeats", type=int, default=0, help="S > 0: time repeated cross-fitting")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -43,6 +52,8 @@ def main():
     n, K = int(a.n), a.folds
     blocked = bool(a.blocked) and a.dtype == "bf16"
     kw = dict(p=a.p, folds=K, seed=a.seed, dtype=a.dtype, device=dev, blocked=blocked, dgp=a.dgp)
+    if a.repeats > 0:
+        return repeated(a, n, K, kw)
     split = synthetic_panel(n, arm_split=True, **kw)
     torch.cuda.synchronize()
 
@@ -96,6 +107,76 @@ def main():
     out["irm_res"] = irm()["res"].cpu().tolist()
     out["irm_mom"] = irm()["mom"].cpu().tolist()
     out["union_support"], out["score_bytes"] = nnz, nbytes
+    print(json.dumps(out))
+
+
+def repeated(a, n, K, kw):
+    import numpy as np
+    import torch
+    from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
+    from ate_replication_causalml_amd.estimators import irm as DI
+    from ate_replication_causalml_amd.estimators.lasso import micro_fold_map
+    from ate_replication_causalml_amd.ops.gram import plan_slot
+    from ate_replication_causalml_amd.utils.graphs import SegmentedStep
+    S = a.repeats
+    micro = synthetic_panel(n, arm_split=True, **{**kw, "folds": K * K})
+    torch.cuda.synchronize()
+    out = {"n": n, "p": a.p, "folds": K, "repeats": S, "dtype": a.dtype,
+           "blocked": kw["blocked"], "dgp": a.dgp}
+    if a.score_only:
+        st = DI.run_phases(DI.irm_repeated_phases(micro, K, S, "min", a.clip))
+        torch.cuda.synchronize()
+        coef = st["coef"]
+        blk = np.stack([s * K + micro_fold_map(K, s) for s in range(S)])
+        gathered = [coef.index_select(0, torch.as_tensor(b, device=coef.device)).contiguous()
+                    for b in blk]
+        for _ in range(5):                      # alternate: both see the same clocks
+            fused = DI.irm_score_moments_multi(micro, coef, blk, a.clip, 2)
+            single = torch.stack([DI.irm_score_moments(micro, c, a.clip, 2) for c in gathered])
+        torch.cuda.synchronize()
+        rows = np.asarray(micro.seg_nreal).reshape(K * K, 2).sum(1)
+        sup = np.stack([(c[:, :, 1:] != 0).any(1).cpu().numpy() for c in gathered])  # [S, K*K, p]
+        out.update(mode="score-only", launches_each=5, smax=DI.score_multi_smax(),
+                   fused_bytes=int((rows * (sup.any(0).sum(1) + 5) * 2).sum()),
+                   single_bytes=int((rows[None] * (sup.sum(2) + 5) * 2).sum()),
+                   union_support_mean=float(sup.any(0).sum(1).mean()),
+                   split_support_mean=float(sup.sum(2).mean()),
+                   same_bits=bool(torch.equal(fused, single)),
+                   splits=st["splits"].cpu().tolist(), mom=fused.cpu().tolist())
+        print(json.dumps(out))
+        return
+    split = synthetic_panel(n, arm_split=True, selection=micro.selection, **kw)
+    torch.cuda.synchronize()
+    with plan_slot(0):
+        one = SegmentedStep(DI.irm_phases(split, K, "min", a.clip), graph=True, warmup=1)
+    with plan_slot(1):
+        rep = SegmentedStep(DI.irm_repeated_phases(micro, K, S, "min", a.clip), graph=True,
+                            warmup=1)
+    for _ in range(a.warmup):
+        one()
+        rep()
+    torch.cuda.synchronize()
+    ms = {"single_x_S": [], "single": [], "repeated": []}
+    for _ in range(a.calls):                      # alternate: both see the same clocks
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(S + 3)]
+        ev[0].record()
+        for s in range(S):
+            one()
+            ev[1 + s].record()
+        rep()
+        ev[S + 1].record()
+        torch.cuda.synchronize()
+        ms["single_x_S"].append(ev[0].elapsed_time(ev[S]))
+        ms["single"] += [ev[s].elapsed_time(ev[s + 1]) for s in range(S)]
+        ms["repeated"].append(ev[S].elapsed_time(ev[S + 1]))
+    out.update(calls=a.calls, graphed=[one.graphed, rep.graphed])
+    for name, v in ms.items():
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "mean_ms": statistics.fmean(v), "spread_ms": max(v) - min(v)}
+    out["saved_ms"] = out["single_x_S"]["median_ms"] - out["repeated"]["median_ms"]
+    st = rep()
+    out["res"], out["splits"] = st["res"].cpu().tolist(), st["splits"].cpu().tolist()
+    out["single_res"] = one()["res"].cpu().tolist()
     print(json.dumps(out))
 
 
