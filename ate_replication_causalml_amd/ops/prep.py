@@ -5,6 +5,8 @@ tensors use the same formulas in float64 torch.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from .. import _native
@@ -31,7 +33,12 @@ def col_moments(X: torch.Tensor) -> torch.Tensor:
         cnt = ok.sum(0).double()
         mean = torch.where(ok, x, 0.0).sum(0) / cnt
         dev = torch.where(ok, x - mean, 0.0)
-        sd = torch.sqrt((dev * dev).sum(0) / (cnt - 1))
+        # fewer than two values: NaN like the kernel and R's sd (0 / -1 would give -0.0).
+        # math.sqrt is correctly rounded, like the kernel's; torch.sqrt on the CPU is within
+        # 1 ulp only on some hosts (two of 68 SDs differed, tests/test_prep.py)
+        var = ((dev * dev).sum(0) / (cnt - 1)).tolist()
+        sd = torch.tensor([math.sqrt(v) if c > 1 else float("nan")
+                           for v, c in zip(var, cnt.tolist())], dtype=torch.float64)
         return torch.stack([cnt, mean, sd], 1)
     Xc = _colmajor(X)
     part = torch.empty(p * CHUNKS * 2, dtype=torch.float64, device=X.device)

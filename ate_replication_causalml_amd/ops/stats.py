@@ -53,15 +53,17 @@ def _naive_finalize(m):
 
 
 def clip_propensity_(p: torch.Tensor, valid: torch.Tensor | None = None):
-    """In place: exact 0 -> min positive, exact 1 -> max below one (ate_functions.R:181-182)."""
+    """In place: exact 0 -> min positive, exact 1 -> max below one (ate_functions.R:181-182).
+    The two limits come from the rows with valid != 0 only; they are applied to every row,
+    padding rows included (csrc/stats.hip clip_apply_kernel: no consumer reads those)."""
     if not p.is_cuda:
         m = torch.ones_like(p, dtype=torch.bool) if valid is None else valid.double() != 0
         pv = p[m]
         pos, below = pv[pv > 0], pv[pv < 1]
         if pos.numel():
-            p[m & (p == 0)] = pos.min()
-        if below.numel():
-            p[m & (p == 1)] = below.max()
+            p[p == 0] = pos.min()
+        if below.numel():                 # after the first rule, as in the reference
+            p[p == 1] = below.max()
         return p
     part = _ws(p.device, 2 * NB)
     _native.call("ate_clip_propensity", p.data_ptr(), 0 if valid is None else valid.data_ptr(),
@@ -171,11 +173,41 @@ def bootstrap_multinomial(e1, e2, B, seed, b0=0):
     return taus
 
 
+# float32 inverse-CDF table of Poisson(1), P(K <= q) for q = 0..7: the constants of
+# csrc/stats.hip poisson1 (tests/test_boot_poisson.py checks them against exp(-1) / q!)
+POISSON1_CDF = (0.36787944, 0.73575888, 0.91969860, 0.98101184,
+                0.99634015, 0.99940582, 0.99991676, 0.99998975)
+
+
+def poisson1_counts(n, seed, stream, row_offset=0):
+    """Poisson(1) resampling counts (int64 [n]) of rows row_offset .. row_offset + n - 1 in
+    replicate ``stream``: #{q < 8 : u >= cdf[q]} with u = float32((w0 >> 8) * 2^-24) and w0
+    word 0 of random_u32(seed, P_BOOT, stream, global row id | 1 << 62), the draw of
+    csrc/stats.hip boot_poisson_kernel. Keyed by the global row id: shard invariant."""
+    import numpy as np
+    idx = (np.arange(n, dtype=np.uint64) + np.uint64(row_offset)) | (np.uint64(1) << np.uint64(62))
+    w0 = rng.random_u32(seed, rng.P_BOOT, stream, idx)[..., 0]
+    u = (w0 >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    cdf = np.asarray(POISSON1_CDF, dtype=np.float32)
+    return (u[:, None] >= cdf[None, :]).sum(1).astype(np.int64)
+
+
 def bootstrap_poisson_partial(e1, e2, B, seed, b0=0, row_offset=0, nb=512):
     """Poisson(1) streaming bootstrap: per-replicate (sum c e1, sum c ok, sum c e2, sum c) over
     this shard's rows -> [B, 4] (all-reduce across ranks, then tau_b = s1/sok + s2/sc)."""
     if not e1.is_cuda:
-        raise NotImplementedError("poisson bootstrap is a device op")
+        import numpy as np
+        e1n, e2n = e1.double().numpy(), e2.double().numpy()
+        ok = ~np.isnan(e1n)
+        out = np.empty((B, 4))
+        for b in range(B):
+            c = poisson1_counts(e1n.size, seed, b0 + b, row_offset)
+            hit = c > 0                   # a row with count 0 is not read (e2 may hold anything)
+            cf = c[hit].astype(np.float64)
+            okh = ok[hit]
+            out[b] = [(cf[okh] * e1n[hit][okh]).sum(), cf[okh].sum(),
+                      (cf * e2n[hit]).sum(), cf.sum()]
+        return torch.from_numpy(out)
     part = _ws(e1.device, nb * ((B + 63) // 64) * 64 * 4)
     _native.call("ate_boot_poisson", e1.data_ptr(), e2.data_ptr(), e1.numel(), seed, b0, B,
                  row_offset, nb, part.data_ptr(), _stream())

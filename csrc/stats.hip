@@ -126,9 +126,13 @@ __global__ void clip_apply_kernel(double* __restrict__ p, int64_t n, const doubl
   __syncthreads();
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    double pi = p[i];
-    if (pi == 0.0 && lim[0] < INFINITY) p[i] = lim[0];
-    else if (pi == 1.0 && lim[1] > -INFINITY) p[i] = lim[1];
+    // the two rules in sequence, as the reference applies them: when no valid entry lies
+    // strictly inside (0, 1) the first limit is 1 and the second rule sees that row too
+    const double p0 = p[i];
+    double pi = p0;
+    if (pi == 0.0 && lim[0] < INFINITY) pi = lim[0];
+    if (pi == 1.0 && lim[1] > -INFINITY) pi = lim[1];
+    if (pi != p0) p[i] = pi;
   }
 }
 
