@@ -65,7 +65,7 @@ c_double = ctypes.c_double
 # name -> argtypes (restype int). 'p' pointer, 'i' int32, 'l' int64, 'u' uint64, 'd' double
 _SIGS = {
     "ate_gram_bf16": "pliipipipipppp",
-    "ate_gram_bf16_pair": "pllipippipippippp",
+    "ate_gram_bf16_pair": "pllipippipippippiip",
     "ate_gram_bf16_tri": "pllippipippipp",
     "ate_gram_pair_bal": "",
     "ate_last_error": "pi",

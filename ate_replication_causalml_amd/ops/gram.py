@@ -40,6 +40,16 @@ GRAM_TRI = os.environ.get("ATE_GRAM_TRI", "0") == "1"
 # bytes (csrc/gram.hip): 896 instead of 1,024 bytes per row, the same Gram bits.
 # ATE_GRAM_BYTES=0 reads them as bf16 (A/B).
 BYTE_COLS = os.environ.get("ATE_GRAM_BYTES", "1") == "1"
+# K-loop schedule of the paired-tile kernel (csrc/gram.hip SCHED_*): "lockstep" (all eight
+# waves run one program, one barrier per 64-row stage) or "stagger" (waves 4-7 run half a
+# stage behind their SIMD partners 0-3: 4.55 -> 4.45 ms per ate_dml call at N = 1e7, p = 500,
+# profiles/gram_handoff). Same Gram bits. ATE_GRAM_SCHED selects.
+SCHEDULES = {"lockstep": 0, "stagger": 1}
+GRAM_SCHED = os.environ.get("ATE_GRAM_SCHED", "stagger")
+# s_setprio 1 for waves 4-7 of that kernel: 0 = none, 1 = every workgroup, 2 = diagonal-pair
+# workgroups only; -1 = the library's default (none under stagger, csrc/gram.hip GRAM_PRIO = 2
+# under lockstep). ATE_GRAM_PRIO (A/B).
+GRAM_PRIO = int(os.environ.get("ATE_GRAM_PRIO", "-1"))
 PLAN_CACHE_MAX = int(os.environ.get("ATE_GRAM_PLAN_CACHE", 8))
 
 _plan_cache: dict = {}
@@ -302,6 +312,13 @@ def clear_plans():
 _STAGES = {"all": 3, "tiles": 1, "reduce": 2}
 
 
+def _sched_for(cs: int) -> int:
+    """The native schedule id of GRAM_SCHED. The schedules other than lockstep address a
+    copy's columns with 32-bit byte offsets from a wave-uniform base (csrc/gram.hip SADDR):
+    a panel whose column stride is 2^28 elements or more runs lockstep, the same bits."""
+    return SCHEDULES[GRAM_SCHED] if cs < (1 << 28) else SCHEDULES["lockstep"]
+
+
 EXACT_LIMB_BOUND = 2.0 ** 38   # |Gram entry| bound of the fixed 2^24-scale int64 limbs
 
 
@@ -374,7 +391,8 @@ def gram(panel: DevicePanel, w: torch.Tensor | None = None, done: torch.Tensor |
         _native.call("ate_gram_bf16_pair", X.data_ptr(), cs, bs, panel.P, pl.tiles.data_ptr(),
                      pl.ntiles, pl.blocks.data_ptr(), pl.chunks.data_ptr(), pl.nchunks,
                      pl.seg_chunk0.data_ptr(), panel.nseg, pl.slab.data_ptr(), G.data_ptr(),
-                     _STAGES[stage], Gx, None if x8 is None or not BYTE_COLS else x8.data_ptr(), s)
+                     _STAGES[stage], Gx, None if x8 is None or not BYTE_COLS else x8.data_ptr(),
+                     _sched_for(cs), GRAM_PRIO, s)
         return pl.Gx if exact else G
     if stage == "reduce":
         return pl.Gx if exact else G

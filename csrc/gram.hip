@@ -134,6 +134,11 @@ constexpr int GK = 64;
 #define GRAM_CPOL 0   // cache policy of the panel stream (2 = nt), A/B builds only
 #endif
 
+typedef const __attribute__((address_space(1))) char* gptr_t;   // a global-memory address
+__device__ __forceinline__ void glds16(gptr_t src, bf16_t* lds_base) {
+  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(lds_base), 16, 0,
+                                   GRAM_CPOL);
+}
 __device__ __forceinline__ void glds16(const void* src, bf16_t* lds_base) {
   __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(lds_base), 16, 0,
                                    GRAM_CPOL);
@@ -357,9 +362,24 @@ __device__ __forceinline__ bf16x8 bytes_to_bf16x8(uint2 d) {
 }
 constexpr int PAIR_BYTE0 = 384;   // first one-byte column (P == 512)
 
+// Schedules of the double-buffered K-loop (ate_gram_bf16_pair `sched`, ops/gram.py GRAM_SCHED):
+// lockstep: all eight waves run one program; stagger: waves 4-7 run half a stage behind their
+// SIMD partners 0-3 (LATE below). An L2 warm-ahead of the panel stream was measured with both
+// and dropped (profiles/gram_handoff).
+constexpr int SCHED_LOCKSTEP = 0, SCHED_STAGGER = 1;
+
 // BYTES: the launch streams one-byte columns (X8 != null); BY: this wave's B fragments
 // (rectangle) or all its fragments (triangle) are byte columns.
-template <int MODE, bool BYTES, bool BY>
+// LATE (waves 4-7 of the stagger schedule): the K-loop is rotated by half a stage. Between
+// barriers s-1 and s the wave multiplies half 1 of stage s-1 from the registers that hold it
+// since before barrier s-1 (beside its reads of half 0 of stage s), issues its copies of stage
+// s+1, then multiplies half 0 of stage s beside its reads of half 1 of stage s; the last half 1
+// follows the last barrier. So while waves 0-3 of the same SIMDs issue their copies and wait
+// for their first fragments, the matrix pipe runs the late waves' held half. Every wave still
+// reads stage s from LDS only between barriers s-1 and s and executes 1 + nsteps barriers
+// (the loop's barriers sit outside every role- or idle-dependent branch), and every
+// accumulator still adds half 0 then half 1 of the stages in stage order: the same bits.
+template <int MODE, bool BYTES, bool BY, bool LATE, bool SADDR>
 __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t cs, int64_t bs, int a0,
                                           int b0, bool haveB, bool idle, int abuf, int bbuf,
                                           int arow0, int bcol0, const Chunk& ch,
@@ -431,7 +451,43 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
   // depends on q); `second` = the chunk's type-1 workgroup
   const int qw = (GRAM_CROSS == 1 && second) ? ((wid + 4) & 7) : wid;
   const bool bfirst = GRAM_CROSS == 2 && second && haveB;
+  // SADDR (the schedules other than lockstep): every piece's address is a wave-uniform base
+  // plus ONE per-lane byte offset -- lane l of a piece reads chunk (l & 7) ^ (l >> 3) of column
+  // l >> 3 of its 8 columns, whichever piece it is -- so the copies need one address register
+  // instead of a pointer per piece (the late waves have none to spare)
+  const int wu = __builtin_amdgcn_readfirstlane(wid);
+  const uint32_t voff_ = (uint32_t)(((lane >> 3) * cs + (((lane & 7) ^ (lane >> 3)) << 3)) * 2);
+  const uint32_t voff8_ = (uint32_t)((lane >> 2) * GK + (((lane & 3) ^ ((lane >> 3) & 2)) << 4));
   auto stage = [&](int st, int64_t i0) {
+    if constexpr (SADDR) {
+      static_assert(!SADDR || GRAM_CROSS == 0, "crossed issue orders: lockstep schedule only");
+      gptr_t Xk0 = (gptr_t) reinterpret_cast<const char*>(X + (i0 >> 6) * bs);
+      // (opaque per stage: a sum of base and offset hoisted out of the K-loop would be a
+      // 64-bit pointer per piece again)
+      uint32_t voff = voff_, voff8 = voff8_;
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" : "+v"(voff), "+v"(voff8));
+#endif
+      const int nbp = 2;              // bytes: B pieces per wave of its bf16 half
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int q = wu * 4 + r;
+        glds16(Xk0 + (int64_t)(a0 + q * 8) * cs * 2 + voff, &lds[st][0][q * 8 * GK]);
+        if (!BYTES && haveB)
+          glds16(Xk0 + (int64_t)(b0 + q * 8) * cs * 2 + voff, &lds[st][1][q * 8 * GK]);
+      }
+      if constexpr (BYTES) {
+#pragma unroll
+        for (int r = 0; r < nbp; ++r) {
+          const int q = wu * 2 + r;
+          glds16(Xk0 + (int64_t)(b0 + q * 8) * cs * 2 + voff, &lds[st][1][q * 8 * GK]);
+        }
+        glds16((gptr_t) reinterpret_cast<const char*>(X8) + (i0 >> 6) * (128 * GK) + wu * 1024 + voff8,
+               reinterpret_cast<bf16_t*>(reinterpret_cast<uint8_t*>(&lds[st][1][128 * GK]) +
+                                         wu * 1024));
+      }
+      return;
+    }
     if constexpr (BYTES) {
       // A: 32 pieces of 8 bf16 columns (4 per wave); B: 16 pieces of its bf16 half (2 per
       // wave) and 8 pieces of 16 byte columns (1 per wave)
@@ -490,13 +546,151 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
   if (nsteps > 0) stage(0, ch.row0);
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
   __syncthreads();
+  // LATE: half 1 of the stage before (zeros ahead of stage 0: they add +0 to the +0 sums)
+  static_assert(!LATE || GRAM_PRELOAD, "the stagger schedule builds on the preload schedules");
+  bf16x8 ha[LATE ? 8 : 1], hb[LATE && !TRI ? 4 : 1];
+  if constexpr (LATE) {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) ha[m] = bf16x8{};
+    if constexpr (!TRI) {
+#pragma unroll
+      for (int n = 0; n < 4; ++n) hb[n] = bf16x8{};
+    }
+  }
+  const bool work = !idle && GRAM_DIAG != 1 && GRAM_DIAG != 3;
   for (int64_t s = 0; s < nsteps; ++s) {
     const int cur = s & 1;
+    const bf16_t* As = lds[cur][abuf];
+    const bf16_t* Bs = lds[cur][bbuf];
+    if constexpr (LATE) {
+      // half 1 of stage s-1 from registers beside the reads of half 0 of stage s ...
+      bf16x8 na[8], nb[TRI ? 1 : 4];
+      uint4 raw[BY ? (TRI ? 8 : 4) : 1];
+      const int c0 = lane >> 4, c1 = 4 + (lane >> 4);
+      if (work) {
+        if constexpr (BY && !TRI) {
+#pragma unroll
+          for (int n = 0; n < 4; ++n) raw[n] = raw16(Bs, bcol0 + n * 16 + (lane & 15));
+#pragma unroll
+          for (int m = 0; m < 8; ++m) na[m] = frag(As, arow0 + m * 16 + (lane & 15), c0);
+          // (the raw B bytes stay raw until the second block: 16 registers fewer here)
+          pair_mfma<MODE>(acc, ha, hb);
+#pragma unroll
+          for (int i = 0; i < 12; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 12, 0);
+        } else if constexpr (BY) {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) raw[m] = raw16(As, arow0 + m * 16 + (lane & 15));
+#pragma unroll
+          for (int m = 0; m < 8; ++m) na[m] = bytes_to_bf16x8(make_uint2(raw[m].x, raw[m].y));
+          pair_mfma<MODE>(acc, ha, ha);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 24, 0);
+        } else if constexpr (!TRI) {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) na[m] = frag(As, arow0 + m * 16 + (lane & 15), c0);
+#pragma unroll
+          for (int n = 0; n < 4; ++n) nb[n] = frag(Bs, bcol0 + n * 16 + (lane & 15), c0);
+          pair_mfma<MODE>(acc, ha, hb);
+#pragma unroll
+          for (int i = 0; i < 12; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 12, 0);
+        } else {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) na[m] = frag(As, arow0 + m * 16 + (lane & 15), c0);
+          pair_mfma<MODE>(acc, ha, ha);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 8, 0);
+        }
+      }
+      // ... the copies of stage s+1 behind those MFMAs ...
+#if GRAM_DIAG != 2
+      if (s + 1 < nsteps) stage(cur ^ 1, ch.row0 + (s + 1) * GK);
+#endif
+      // ... and half 0 of stage s beside the reads of its half 1 into the registers just freed
+      if (work) {
+        if constexpr (BY && !TRI) {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) ha[m] = frag(As, arow0 + m * 16 + (lane & 15), c1);
+#pragma unroll
+          for (int n = 0; n < 4; ++n) nb[n] = bytes_to_bf16x8(make_uint2(raw[n].x, raw[n].y));
+#pragma unroll
+          for (int n = 0; n < 4; ++n) hb[n] = bytes_to_bf16x8(make_uint2(raw[n].z, raw[n].w));
+          pair_mfma<MODE>(acc, na, nb);
+          __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);      // B fragment 0 of half 0
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {                           // fragments 1-3 beside the
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // first MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 27, 0);
+        } else if constexpr (BY) {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) ha[m] = bytes_to_bf16x8(make_uint2(raw[m].z, raw[m].w));
+          pair_mfma<MODE>(acc, na, na);
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 16, 0);
+        } else if constexpr (!TRI) {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) ha[m] = frag(As, arow0 + m * 16 + (lane & 15), c1);
+#pragma unroll
+          for (int n = 0; n < 4; ++n) hb[n] = frag(Bs, bcol0 + n * 16 + (lane & 15), c1);
+          pair_mfma<MODE>(acc, na, nb);
+#pragma unroll
+          for (int i = 0; i < 12; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 12, 0);
+        } else {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) ha[m] = frag(As, arow0 + m * 16 + (lane & 15), c1);
+          pair_mfma<MODE>(acc, na, na);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 8, 0);
+        }
+      }
+    } else {
 #if GRAM_DIAG != 2
     if (s + 1 < nsteps) stage(cur ^ 1, ch.row0 + (s + 1) * GK);
 #endif
-    const bf16_t* As = lds[cur][abuf];
-    const bf16_t* Bs = lds[cur][bbuf];
 #if GRAM_PRELOAD
     // every fragment of the stage (both 32-row halves) read from LDS up front, then the
     // MFMAs: the waits on LDS leave the MFMA chains of the stage
@@ -619,10 +813,14 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
       }
     }
 #endif
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): next stage landed
 #if GRAM_DIAG != 5
     __syncthreads();
 #endif
+  }
+  if constexpr (LATE) {
+    if (work) pair_mfma<MODE>(acc, ha, TRI ? ha : hb);      // half 1 of the last stage
   }
 #endif
   if (idle) return;
@@ -648,11 +846,13 @@ extern "C" __attribute__((visibility("default"))) int ate_gram_clock_reset() {
 }
 #endif
 
-template <bool BYTES>
+// SCHED: the K-loop schedule (SCHED_*; the ring build has one). prio: s_setprio 1 for waves
+// 4-7 (0 = none, 1 = every workgroup, 2 = diagonal-pair workgroups only; GRAM_PRIO).
+template <bool BYTES, int SCHED>
 __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
     const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int4* __restrict__ tiles, int ntiles,
     const Chunk* __restrict__ chunks, int nchunks, float* __restrict__ slab,
-    const uint8_t* __restrict__ X8) {
+    const uint8_t* __restrict__ X8, int prio) {
   __shared__ __attribute__((aligned(16))) bf16_t lds[PAIR_LDS];   // 128 KB (ring: up to 160)
 #ifdef GRAM_CLOCK
   const unsigned long long gc0 = clock64(), gw0 = wall_clock64();
@@ -685,26 +885,30 @@ __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
   constexpr int RS = PairRole<PAIR_RECT_D0>::NB, TS = PairRole<PAIR_TRI>::NB;  // 34 / 34 (32 / 36)
   const int base = type == 0 ? wid * 32 : tri ? 4 * RS + (wid - 4) * TS : wid * RS;
   float* out = slab + ((int64_t)c * ntiles + t) * (PAIR_SLOTS * 256) + (int64_t)base * 256;
-#if GRAM_PRIO
   // the second-dispatched half (waves 4-7: the triangle waves of a diagonal pair, the
   // heavier role) loses VALU / LDS issue arbitration to the older half on every stage;
-  // one static priority raise for it (uniform branches: readfirstlane, type)
-#if GRAM_PRIO == 2
-  if (type != 0 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-#else
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-#endif
-#endif
+  // one static priority raise for it (uniform branches: readfirstlane, type, prio)
+  if ((prio == 1 || (prio == 2 && type != 0)) &&
+      __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)
+    __builtin_amdgcn_s_setprio(1);
   // byte fragments: tile b's columns 128..255 (type 0: the waves of B columns 128..255;
   // type 1, tile b: the rectangle waves' B and the second triangle)
   const bool by = BYTES && (type == 0 ? (wid & 3) >= 2 : region == 1 && (!tri || half == 1));
   ATE_DASSERT(!BYTES || (X8 != nullptr && ntiles == 2 && b0 == 256));
-#define PAIR_WAVE(M, B) pair_wave<M, BYTES, B>(X, cs, bs, a0, b0, haveB, idle, abuf, bbuf, arow0, \
-                                               bcol0, ch, lds, out, type != 0, X8)
-  if (tri) { if (by) PAIR_WAVE(PAIR_TRI, BYTES); else PAIR_WAVE(PAIR_TRI, false); }
-  else if (type == 0) { if (by) PAIR_WAVE(PAIR_RECT, BYTES); else PAIR_WAVE(PAIR_RECT, false); }
-  else if (half == 0) { if (by) PAIR_WAVE(PAIR_RECT_D0, BYTES); else PAIR_WAVE(PAIR_RECT_D0, false); }
-  else { if (by) PAIR_WAVE(PAIR_RECT_D1, BYTES); else PAIR_WAVE(PAIR_RECT_D1, false); }
+  // waves 4-7 (the triangle waves of a diagonal pair, half of the rectangle waves of an
+  // off-diagonal tile) are the late ones of the stagger schedule
+  constexpr bool STAG = (SCHED & SCHED_STAGGER) != 0 && !GRAM_RING;
+#define PAIR_WAVE(M, B, L) pair_wave<M, BYTES, B, L, SCHED != SCHED_LOCKSTEP>(                      \
+      X, cs, bs, a0, b0, haveB, idle, abuf, bbuf, arow0, bcol0, ch, lds, out, type != 0, X8)
+#define PAIR_WAVE_BY(M, L) do { if (by) PAIR_WAVE(M, BYTES, L); else PAIR_WAVE(M, false, L); } while (0)
+  if (tri) PAIR_WAVE_BY(PAIR_TRI, STAG);
+  else if (type == 0) {
+    if (STAG && __builtin_amdgcn_readfirstlane(wid) >= 4) PAIR_WAVE_BY(PAIR_RECT, STAG);
+    else PAIR_WAVE_BY(PAIR_RECT, false);
+  }
+  else if (half == 0) PAIR_WAVE_BY(PAIR_RECT_D0, false);
+  else PAIR_WAVE_BY(PAIR_RECT_D1, false);
+#undef PAIR_WAVE_BY
 #undef PAIR_WAVE
 #ifdef GRAM_CLOCK
   __syncthreads();
@@ -1008,8 +1212,15 @@ __global__ void gram_pair_reduce_kernel(const float* __restrict__ slab, const in
   }
 }
 
-ATE_KERNEL_SHAPE("gram_bf16_pair_kernel", 512, 0, gram_bf16_pair_kernel<false>)
-ATE_KERNEL_SHAPE("gram_bf16_pair_kernel<bytes>", 512, 0, gram_bf16_pair_kernel<true>)
+// the schedules built into the library (X-macro: registration and launch below)
+#define PAIR_SCHEDS(F) F(0) F(1)
+#define PAIR_SHAPE(S)                                                                     \
+  static ate::KernelShapeReg ate_kshape_pair_##S(                                         \
+      (const void*)(gram_bf16_pair_kernel<false, S>), "gram_bf16_pair_kernel<sched " #S ">", 512, 0); \
+  static ate::KernelShapeReg ate_kshape_pair8_##S(                                        \
+      (const void*)(gram_bf16_pair_kernel<true, S>), "gram_bf16_pair_kernel<bytes, sched " #S ">", 512, 0);
+PAIR_SCHEDS(PAIR_SHAPE)
+#undef PAIR_SHAPE
 ATE_KERNEL_SHAPE("gram_bf16_tri_kernel", 512, 0, gram_bf16_tri_kernel)
 ATE_KERNEL_SHAPE("gram_bf16_256_kernel", 512, 0, gram_bf16_256_kernel)
 ATE_KERNEL_SHAPE("gram_bf16_kernel", 256, 0, gram_bf16_kernel)
@@ -1020,20 +1231,35 @@ ATE_KERNEL_SHAPE("gram_bf16_kernel", 256, 0, gram_bf16_kernel)
 ATE_API int ate_gram_bf16_pair(const void* X, int64_t cs, int64_t bs, int P, const void* tiles, int ntiles,
                                const void* blocks, const void* chunks, int nchunks,
                                const void* seg_chunk0, int nseg, void* slab, void* G, int what,
-                               void* Gx, const void* X8, void* stream) {
+                               void* Gx, const void* X8, int sched, int prio, void* stream) {
   if (P % (2 * GT) || what < 1 || what > 3) return -1;
   if (X8 != nullptr && (P != 512 || ntiles != 2 || GRAM_RING)) return -1;
+  if (GRAM_RING && sched != SCHED_LOCKSTEP) return -1;
+  // the other schedules address a piece's 8 columns with a 32-bit per-lane byte offset
+  if (sched != SCHED_LOCKSTEP && cs >= ((int64_t)1 << 28)) return -1;
+  // the priority raise was tuned for lockstep; with the stagger it measures as no gain
+  // (profiles/gram_handoff: none 4.446, diagonal pairs 4.465, everywhere 4.476 ms per call)
+  if (prio < 0) prio = sched == SCHED_STAGGER ? 0 : GRAM_PRIO;
+  if (prio > 2) return -1;
   hipStream_t s = (hipStream_t)stream;
   if (what & 1) {
-  if (X8 != nullptr)
-    ATE_LAUNCH(gram_bf16_pair_kernel<true>, dim3(nchunks * ntiles), dim3(512), 0, s,
-               (const bf16_t*)X, cs, bs, (const int4*)tiles, ntiles, (const Chunk*)chunks,
-               nchunks, (float*)slab, (const uint8_t*)X8);
-  else
-    ATE_LAUNCH(gram_bf16_pair_kernel<false>, dim3(nchunks * ntiles), dim3(512), 0, s,
-               (const bf16_t*)X, cs, bs, (const int4*)tiles, ntiles, (const Chunk*)chunks,
-               nchunks, (float*)slab, (const uint8_t*)nullptr);
-  ATE_CHECK_LAUNCH();
+    switch (sched) {
+#define PAIR_LAUNCH(S)                                                                        \
+  case S:                                                                                     \
+    if (X8 != nullptr)                                                                        \
+      ATE_LAUNCH((gram_bf16_pair_kernel<true, S>), dim3(nchunks * ntiles), dim3(512), 0, s,   \
+                 (const bf16_t*)X, cs, bs, (const int4*)tiles, ntiles, (const Chunk*)chunks,  \
+                 nchunks, (float*)slab, (const uint8_t*)X8, prio);                            \
+    else                                                                                      \
+      ATE_LAUNCH((gram_bf16_pair_kernel<false, S>), dim3(nchunks * ntiles), dim3(512), 0, s,  \
+                 (const bf16_t*)X, cs, bs, (const int4*)tiles, ntiles, (const Chunk*)chunks,  \
+                 nchunks, (float*)slab, (const uint8_t*)nullptr, prio);                       \
+    break;
+      PAIR_SCHEDS(PAIR_LAUNCH)
+#undef PAIR_LAUNCH
+      default: return -1;   // a schedule this library was not built with
+    }
+    ATE_CHECK_LAUNCH();
   }
   if (what & 2) {
     const int64_t total = (int64_t)nseg * ntiles * PAIR_SLOTS * 256;

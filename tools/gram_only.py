@@ -1,5 +1,7 @@
 """Run the bf16 Gram kernel alone on the N=1e7, p=500 bench panel (A/B of the 256-tile
-kernel variants, and for PMC profiling). Usage: gram_only.py [N] [tri|pair|tile256 ...]; ATE_BLOCKED=0 for a column-major panel"""
+kernel variants, and for PMC profiling). Usage: gram_only.py [N] [tri|pair|tile256 ...];
+pair and pair16 take a K-loop schedule suffix (pair:lockstep, pair:stagger: ops/gram.py
+SCHEDULES); ATE_BLOCKED=0 for a column-major panel"""
 import os
 import sys
 
@@ -19,7 +21,10 @@ pan = synthetic_panel(n, p=500, folds=5, seed=1991, dtype="bf16", device=torch.d
                       dgp=os.environ.get("ATE_DGP", "tutorial"))
 ref = None
 stage = os.environ.get("ATE_GRAM_STAGE", "all")   # "tiles": the tile kernel alone (no slab reduce)
-for v in variants:
+sched0 = gram_mod.GRAM_SCHED
+for name in variants:
+    v, _, sched = name.partition(":")
+    gram_mod.GRAM_SCHED = sched or sched0
     # "tri": the split-triangle kernel (P == 512); "pair": the paired-tile kernel
     gram_mod.GRAM_KERNEL = "pair" if v in ("tri", "pair16") else v
     gram_mod.GRAM_TRI = v == "tri"
@@ -37,5 +42,5 @@ for v in variants:
     G = G.clone()
     diff = 0.0 if ref is None else float((G - ref).abs().max() / ref.abs().max())
     ref = G if ref is None else ref
-    print(f"kernel {v}: gram ms {e[0].elapsed_time(e[1]) / 10:.3f}  rel-diff vs first {diff:.2e}",
+    print(f"kernel {name}: gram ms {e[0].elapsed_time(e[1]) / 10:.3f}  rel-diff vs first {diff:.2e}",
           flush=True)

@@ -1,8 +1,10 @@
 """A/B of the single ate_dml call (bench.py's timed step) over Gram kernels on ONE panel:
 the panel is generated once, each variant's step is captured and timed in alternation
 (K calls back to back, R rounds), so box-to-box and clock drift cancel out.
-Usage: single_ab.py [tri,pair] [rounds] [calls]   (variants: tri | pair | pair16, with an
-optional @rN suffix: the paired Gram's plan built for N whole rounds of workgroups)"""
+Usage: single_ab.py [tri,pair] [rounds] [calls]   (variants: tri | pair | pair16, with
+optional suffixes :SCHED -- a K-loop schedule of ops/gram.py SCHEDULES, e.g. pair:lockstep,
+pair:stagger --, /pN -- s_setprio for waves 4-7: 0 none, 1 all, 2 diagonal pairs -- and @rN
+-- the paired Gram's plan built for N whole rounds of workgroups; in that order)"""
 import os
 import sys
 import time
@@ -27,8 +29,15 @@ pan = synthetic_panel(int(1e7), p=500, folds=5, seed=1991, dtype="bf16", blocked
                       dgp=os.environ.get("ATE_DGP", "tutorial"))
 seg = global_seg_counts(pan, LocalComm())
 steps = {}
+_SCHED0, _PRIO0 = gram_mod.GRAM_SCHED, gram_mod.GRAM_PRIO
+
+
 def _select(v):
     v, _, r = v.partition("@r")
+    v, _, prio = v.partition("/p")
+    v, _, sched = v.partition(":")
+    gram_mod.GRAM_SCHED = sched or _SCHED0
+    gram_mod.GRAM_PRIO = int(prio) if prio else _PRIO0
     gram_mod.GRAM_TRI = v == "tri"
     gram_mod.BYTE_COLS = v != "pair16"      # pair16: the byte columns read as bf16
     if r:
