@@ -24,7 +24,9 @@ cate(basis) / confint(joint=True)) -> ate_dml_irm_cate;
 the exact depth-2 policy tree on its scores (DoubleML policy_tree, searched exactly as
 policytree does) -> ate_dml_irm_policy;
 its sensitivity to unobserved confounding (DoubleML sensitivity_analysis /
-sensitivity_benchmark) -> ate_dml_irm_sensitivity.
+sensitivity_benchmark) -> ate_dml_irm_sensitivity;
+its effect on the treated and on the controls with the joint covariance (DoubleML
+IRM(score="ATTE"), grf average_treatment_effect(target.sample=)) -> ate_dml_irm_targets.
 """
 from __future__ import annotations
 
@@ -34,7 +36,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import AteResult, CateResult, GateResult, PolicyTreeResult, SensitivityResult, format_table, results_frame
+from .result import (AteResult, CateResult, GateResult, PolicyTreeResult, SensitivityResult, TargetResult,
+                     format_table, results_frame)
 from .utils import guards
 from .utils.tracing import trace
 
@@ -355,6 +358,29 @@ def ate_dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, 
                                       clip=clip, device=run.device(), dtype=run.dtype)
 
 
+def ate_dml_irm_targets(Y, W, X, targets=("all", "treated", "control"), folds=5,
+                        lambda_rule="min", clip=0.01, run=None, repeats=1) -> TargetResult:
+    """The average effect of ate_dml_irm over other target populations: on the treated
+    ("treated", the ATT; DoubleML IRM(score="ATTE"), grf target.sample = "treated") and on
+    the controls ("control", the ATC), beside everyone ("all", the ATE of ate_dml_irm), with
+    their joint covariance: ``result.contrast("treated", "control")`` tests whether the two
+    effects differ (estimators/targets.py). Only the nuisances that ``targets`` need are
+    fitted (the effect on the treated needs no g1, that on the controls no g0); the rows of
+    the targets that were not requested are NaN. W must be binary. Repeated cross-fitting
+    (``repeats`` other than 1) and group, curve and policy versions of these targets are not
+    available."""
+    run = _run(run)
+    with trace("ate_dml_irm_targets", folds=folds):
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_irm_targets(Y, W, X, targets, folds=folds, seed=run.seed,
+                                     lambda_rule=lambda_rule, clip=clip, repeats=repeats)
+        from .estimators import targets as DT
+        return DT.dml_irm_targets(Y, W, X, targets, folds=folds, seed=run.seed,
+                                  lambda_rule=lambda_rule, clip=clip, device=run.device(),
+                                  dtype=run.dtype, repeats=repeats)
+
+
 def ate_residual_balance(Y, W, X, balance: BalanceConfig | None = None,
                          method="residual_balancing", run=None) -> AteResult:
     """E14 residual_balance_ATE (ate_functions.R:393-405) -> balanceHD::residualBalance.ate."""
@@ -528,7 +554,7 @@ def replicate(data=None, config: ReplicateConfig | None = None, log_path=None, p
 __all__ = [
     "ate_naive", "ate_ols", "propensity_logistic", "propensity_lasso", "ate_ipw", "ate_ipw_wls",
     "ate_lasso_single", "ate_lasso", "ate_aipw_rf", "ate_aipw_glm", "ate_belloni",
-    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_policy", "ate_dml_irm_sensitivity", "ate_residual_balance", "ate_causal_forest", "replicate",
+    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_policy", "ate_dml_irm_sensitivity", "ate_dml_irm_targets", "ate_residual_balance", "ate_causal_forest", "replicate",
     "ate_aipw_crossfit", "ate_causal_forest_bootstrap",
-    "Replication", "AteResult", "CateResult", "GateResult", "PolicyTreeResult", "SensitivityResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
+    "Replication", "AteResult", "CateResult", "GateResult", "PolicyTreeResult", "SensitivityResult", "TargetResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
 ]

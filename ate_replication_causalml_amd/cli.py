@@ -47,9 +47,9 @@ def _dml(a):
         if a.repeats > 1:
             # repeated cross-fitting: 2 K*K micro-arm segments, `repeats` K-fold partitions
             if (a.gate_col is not None or a.cate_col is not None or a.policy_cols is not None
-                    or a.sensitivity):
+                    or a.sensitivity or a.targets is not None):
                 raise SystemExit("--repeats applies to the ATE only: not with --gate-col, "
-                                 "--cate-col, --policy-cols or --sensitivity")
+                                 "--cate-col, --policy-cols, --sensitivity or --targets")
             from .estimators.irm import irm_repeated_panel
             pan = synthetic_panel(a.n, p=a.p, folds=a.folds * a.folds, seed=a.seed,
                                   dtype=a.dtype, device=dev, arm_split=True)
@@ -64,8 +64,31 @@ def _dml(a):
                               "aggregate": a.aggregate, "splits": splits.cpu().tolist(),
                               "n_clipped": [int(round(v)) for v in mom[:, 3].cpu().tolist()]}))
             return 0
+        if a.targets is not None and (a.gate_col is not None or a.cate_col is not None
+                                      or a.policy_cols is not None or a.sensitivity):
+            raise SystemExit("--targets is an analysis of its own: not with --gate-col, "
+                             "--cate-col, --policy-cols or --sensitivity")
         pan = synthetic_panel(a.n, p=a.p, folds=a.folds, seed=a.seed, dtype=a.dtype, device=dev,
                               arm_split=True)
+        if a.targets is not None:
+            # the effect over everyone, on the treated and on the controls, joint covariance
+            from .estimators.targets import irm_targets_panel
+            from .result import TARGETS, TargetResult, check_targets
+            try:
+                tg = check_targets([t for t in a.targets.split(",") if t])
+            except ValueError as e:
+                raise SystemExit(str(e))
+            tg = tuple(t for t in TARGETS if t in tg)
+            mom, _ = irm_targets_panel(pan, a.folds, tg, a.lambda_rule, a.clip)
+            v = mom.double().cpu().numpy()
+            r = TargetResult.from_moments("DML-IRM target populations (LASSO)", v, tg, n=a.n)
+            out = {"targets": list(r.targets), "estimates": r.rows(), "cov": r.cov,
+                   "n_treated": int(round(float(v[11]))), "n_clipped": int(round(float(v[3])))}
+            if "treated" in tg and "control" in tg:
+                from dataclasses import asdict
+                out["contrast"] = asdict(r.contrast("treated", "control"))
+            print(json.dumps(out))
+            return 0
         if a.gate_col is not None and a.sensitivity:
             raise SystemExit("--gate-col and --sensitivity are separate analyses: pick one")
         if a.cate_col is not None and (a.gate_col is not None or a.sensitivity):
@@ -262,6 +285,9 @@ def main(argv=None):
                    help="irm --sensitivity: the hypothesis of the robustness values")
     d.add_argument("--benchmark-cols", action="append", metavar="J,J,...",
                    help="irm --sensitivity: benchmark the covariate set x{J}, ... (repeatable)")
+    d.add_argument("--targets", default=None, metavar="T,T,...",
+                   help="irm: the effect over these target populations (all, treated, control) "
+                        "with their joint covariance")
     d.set_defaults(fn=_dml)
     b = sub.add_parser("build")
     b.set_defaults(fn=_build)

@@ -20,9 +20,10 @@ Repeated cross-fitting (:func:`dml_irm_lasso_repeated`, :func:`irm_repeated_phas
 partitions built from K*K micro-groups on a 2 K*K-segment panel share one Gram pass and one
 multi-split score pass (:func:`irm_score_moments_multi`), median-aggregated.
 
-The estimators on the same score (gate, cate, policy, sensitivity) share what lives here: the
-score pass in its three forms (:func:`irm_score_moments`, :func:`irm_sens_moments`,
-:func:`irm_scores` -- one CPU twin ``_score_terms``, one launcher ``_score_launch``), the
+The estimators on the same score (gate, cate, policy, sensitivity, targets) share what lives
+here: the score pass in its forms (:func:`irm_score_moments`, :func:`irm_sens_moments`,
+:func:`irm_target_moments`, :func:`irm_scores` -- one CPU twin ``_score_terms``, one launcher
+``_score_launch``), the
 front end of every ``dml_irm_*`` function (:func:`arm_split_panel`, :func:`run_body`,
 :func:`comm_counts`), the fit and score phases (:func:`irm_fit_phases`, :func:`phase_scores`,
 :func:`run_phases`) and the n - 1 variance rule (:func:`mean_se`).
@@ -38,7 +39,7 @@ from ..ops.enet import (MAX_PATH_PROBLEMS, cv_enet_gaussian, cv_problem_count,
                         default_lambda_min_ratio)
 from ..ops.gram import gram
 from ..ops.panel import build_panel, dtype_code
-from ..result import SENS_MOMENTS, AteResult
+from ..result import SENS_MOMENTS, TARGET_MOMENTS, AteResult
 from ..utils.graphs import estimator_graphs
 from .common import as_np, resolve_device
 from .lasso import (_fold_ids, _tri_index, allreduce_sym_, global_seg_counts, median_aggregate,
@@ -224,6 +225,40 @@ def irm_sens_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold:
     return mom
 
 
+def irm_target_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
+                       nbx: int | None = None) -> torch.Tensor:
+    """The pass of :func:`irm_score_moments` -- same arguments, same dot products, same psi --
+    accumulating the 12 fp64 moments of the three target populations (``result.TARGET_MOMENTS``;
+    estimators/targets.py): with e the clipped propensity and the two quotients of psi,
+
+        q1 = w (y - g1) / e                q0 = (1 - w)(y - g0) / (1 - e)
+        a  = w (y - g0) - e q0             (the ATT numerator: g0 and m only)
+        c  = -(1 - w)(y - g1) + (1 - e) q1 (the ATC numerator: g1 and m only)
+
+    and psi = a + c algebraically. GPU: csrc/irm.hip ``ate_irm_target_moments`` (for the same
+    ``nbx`` S psi, S psi^2, n, n_clipped and n_treated carry the bits of
+    ``irm_score_moments``); CPU: the float64 torch twin. A zero coefficient row (a nuisance
+    that was not fitted) is legal: the moments that involve it are finite and meaningless."""
+    if pan.data.is_cuda:
+        return _score_launch("ate_irm_target_moments", pan, coef, clip, segs_per_fold, nbx,
+                             len(TARGET_MOMENTS), True)
+    mom = torch.zeros(len(TARGET_MOMENTS), dtype=torch.float64)
+    lo, hi = clip, 1.0 - clip
+    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
+        e = m.clamp(lo, hi)
+        psi = aipw_psi(y, w, g0, g1, e)
+        q1, q0 = w * (y - g1) / e, (1.0 - w) * (y - g0) / (1.0 - e)
+        a = w * (y - g0) - e * q0
+        c = -(1.0 - w) * (y - g1) + (1.0 - e) * q1
+        one = torch.ones_like(psi)
+        mom += torch.stack([psi.sum(), (psi * psi).sum(), one.sum(),
+                            ((m < lo) | (m > hi)).double().sum(),
+                            a.sum(), (a * a).sum(), (a * w).sum(),
+                            c.sum(), (c * c).sum(), (c * (1.0 - w)).sum(), (a * c).sum(),
+                            w.sum()])
+    return mom
+
+
 def irm_scores(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
                nbx: int | None = None) -> torch.Tensor:
     """The per-row AIPW scores psi [ld] (fp64, panel row order, 0 on padding rows): the pass
@@ -293,19 +328,34 @@ def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_cou
     return phases
 
 
-def fit_problems(pan, K: int, counts):
+NUISANCES = (0, 1, 2)   # rows of a coefficient block: g0, g1, m
+
+
+def check_nuisances(nuisances) -> tuple:
+    """A subset of :data:`NUISANCES` (0: g0, 1: g1, 2: m), distinct, ascending, not empty."""
+    nu = tuple(int(r) for r in nuisances)
+    if not nu or any(r not in NUISANCES for r in nu) or list(nu) != sorted(set(nu)):
+        raise ValueError(f"nuisances must be an ascending, non-empty subset of {NUISANCES} "
+                         f"(g0, g1, m), got {tuple(nuisances)}")
+    return nu
+
+
+def fit_problems(pan, K: int, counts, nuisances=NUISANCES):
     """The 3 K nuisance problems on the 3K-Gram stack ``cat([G, G[0::2] + G[1::2]])`` as
     arguments of ``cv_enet_gaussian``: (seg_counts, full_sets, full_y, ycols). Segments of
     the stack: 2s + a = (fold s, arm a); 2K + s = fold s, both arms. ``counts``: (global)
-    rows per panel segment."""
+    rows per panel segment. nuisances: the subset of (0: g0, 1: g1, 2: m) to fit -- only its
+    ``len(nuisances) K`` problems are named, fold by fold in that order."""
+    nuisances = check_nuisances(nuisances)
     counts = np.asarray(counts, dtype=np.float64)
     counts3 = np.concatenate([counts, counts[0::2] + counts[1::2]])
     full_sets, full_y = [], []
     for k in range(K):
         others = [s for s in range(K) if s != k]
-        full_sets += [[2 * s for s in others], [2 * s + 1 for s in others],
-                      [2 * K + s for s in others]]
-        full_y += [0, 0, 1]                       # g0, g1: target Y; m: target W
+        sets = [[2 * s for s in others], [2 * s + 1 for s in others],
+                [2 * K + s for s in others]]
+        full_sets += [sets[r] for r in nuisances]
+        full_y += [(0, 0, 1)[r] for r in nuisances]   # g0, g1: target Y; m: target W
     return counts3, full_sets, full_y, [pan.cols["Y"], pan.cols["W"]]
 
 
@@ -342,10 +392,19 @@ def gram_phases(pan, comm=None):
     return phases, (reduce if dist else None)
 
 
-def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None):
+def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None,
+                   nuisances=NUISANCES):
     """The phases of :func:`irm_phases` up to the fitted coefficients (A, C01, B; state "G",
     "cv", "coef"), shared with the group-effect estimator (estimators/gate.py), and the
-    factory ``reduce(name)`` of an all-reduce phase of a state tensor (None at world 1)."""
+    factory ``reduce(name)`` of an all-reduce phase of a state tensor (None at world 1).
+
+    nuisances: the subset of (0: g0, 1: g1, 2: m) to fit (estimators/targets.py: the effect
+    on the treated needs no g1, the effect on the controls no g0). Only those
+    ``len(nuisances) K K`` problems go into the one path launch; the picked
+    coefficients are scattered into "coef" [K, 3, p+1], whose other rows are zero. The launch
+    keeps the lambda ratio of the whole fit (``default_lambda_min_ratio`` over the training
+    sets of all three nuisances), so a nuisance does not depend on which others are fitted
+    beside it. The default fits all three with today's call."""
     dist = comm is not None and comm.world_size > 1
     K = folds
     if seg_counts is None:
@@ -354,15 +413,28 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
     check_cells(counts, K)
     if pan.nseg != 2 * K:
         raise ValueError(f"DML-IRM needs {2 * K} segments, this shard's panel has {pan.nseg}")
-    counts3, full_sets, full_y, ycols = fit_problems(pan, K, counts)
+    nuisances = check_nuisances(nuisances)
+    counts3, full_sets, full_y, ycols = fit_problems(pan, K, counts, nuisances)
+    subset = nuisances != NUISANCES
+    ratio = None
+    if subset:
+        _, sets_all, _, _ = fit_problems(pan, K, counts)
+        ratio = default_lambda_min_ratio(min(counts3[list(fs)].sum() for fs in sets_all),
+                                         len(pan.xcols))
+        slots = const(nuisances, torch.int64, pan.device)
 
     def phase_fit(st):
         G = st["G"]
         G3 = torch.cat([G, G[0::2] + G[1::2]])
         cv = cv_enet_gaussian(G3, pan, pan.xcols, ycols, full_sets=full_sets,
-                              seg_counts=counts3, full_y=full_y)
-        coef = (cv.coef_min if lambda_rule == "min" else cv.coef_1se).reshape(K, 3, -1)
-        return {**st, "cv": cv, "coef": coef.double().contiguous()}
+                              seg_counts=counts3, full_y=full_y, lambda_min_ratio=ratio)
+        coef = (cv.coef_min if lambda_rule == "min" else cv.coef_1se)
+        if subset:
+            some = coef.reshape(K, len(nuisances), -1).double()
+            coef = torch.zeros(K, 3, some.shape[2], dtype=torch.float64, device=some.device)
+            coef.index_copy_(1, slots, some)
+            return {**st, "cv": cv, "coef": coef}
+        return {**st, "cv": cv, "coef": coef.reshape(K, 3, -1).double().contiguous()}
 
     phases, reduce = gram_phases(pan, comm)
     phases.append(phase_fit)

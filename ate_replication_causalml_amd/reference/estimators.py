@@ -820,6 +820,56 @@ def dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null
                              float(null), rv, rva, rows, diag)
 
 
+def targets_from_rows(y, w, g0, g1, m, clip):
+    """The effects over everyone, on the treated and on the controls with their joint
+    covariance from per-row held-out nuisances (m before clipping), row by row in float64 --
+    written independently of the moment route of result.TargetResult: per-row influence
+    vectors and ``phi @ phi.T``, no closed forms. Returns (theta [3], cov [3, 3]) in the
+    order (all, treated, control). With e the clipped propensity:
+
+        a = w (y - g0) - e (1 - w)(y - g0) / (1 - e)        theta_treated = sum(a) / n1
+        c = -(1 - w)(y - g1) + (1 - e) w (y - g1) / e       theta_control = sum(c) / n0
+        psi = g1 - g0 + w (y - g1) / e - (1 - w)(y - g0) / (1 - e)   theta_all = mean(psi)
+        phi = [psi - theta_all, (a - theta_treated w) / p1, (c - theta_control (1 - w)) / p0]
+        cov = phi phi' / (n - 1) / n
+
+    (the ATTE score of DoubleML's IRM: psi_a theta + psi_b with J = -1; p1 = n1 / n)."""
+    y, w, g0, g1, m = (np.asarray(v, dtype=np.float64) for v in (y, w, g0, g1, m))
+    n = len(y)
+    n1 = w.sum()
+    n0 = n - n1
+    e = np.clip(m, clip, 1 - clip)
+    psi = g1 - g0 + w * (y - g1) / e - (1 - w) * (y - g0) / (1 - e)
+    a = w * (y - g0) - e * ((1 - w) * (y - g0) / (1 - e))
+    c = -(1 - w) * (y - g1) + (1 - e) * (w * (y - g1) / e)
+    theta = np.array([psi.mean(), a.sum() / n1, c.sum() / n0])
+    phi = np.stack([psi - theta[0], (a - theta[1] * w) / (n1 / n),
+                    (c - theta[2] * (1 - w)) / (n0 / n)])
+    return theta, phi @ phi.T / (n - 1) / n
+
+
+def dml_irm_targets(Y, W, X, targets=("all", "treated", "control"), folds=5, seed=1991,
+                    lambda_rule="min", clip=0.01, method="DML-IRM target populations (LASSO)",
+                    fold_ids=None, repeats=1):
+    """The average effect of the cross-fitted interactive model over everyone, on the
+    treated (ATT) and on the controls (ATC) with their joint covariance, the float64 twin of
+    estimators.targets.dml_irm_targets: per-row nuisances from _irm_scores (all three are
+    always fitted here), targets_from_rows for the estimates. The rows of the targets that
+    were not requested are NaN. Repeated cross-fitting of these targets is out of scope."""
+    from ..result import TargetResult, check_targets
+    targets = check_targets(targets)
+    if repeats != 1:
+        raise ValueError("repeated cross-fitting is not available for the target populations: "
+                         "repeats must be 1")
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    _, g0, g1, m = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    theta, cov = targets_from_rows(Y, W, g0, g1, m, clip)
+    return TargetResult.from_estimates(method, theta, cov, targets, n=len(Y),
+                                       n_treated=int(W.sum()),
+                                       n_clipped=int(((m < clip) | (m > 1 - clip)).sum()),
+                                       hipgraph=False)
+
+
 def dml_plr_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="min",
                            aggregate="median", method="DML cross-fit (LASSO, repeated)"):
     """Repeated cross-fitting (Chernozhukov et al. 2018 §3.4, median method): S = repeats

@@ -609,6 +609,166 @@ class SensitivityResult:
                            "moments": self.moments, "diagnostics": keep(self.diagnostics)})
 
 
+# ------------------------------------------------------------ target populations (ATE / ATT / ATC)
+# the 12 moments of the target pass (estimators/targets.py, csrc/irm.hip), with e the clipped
+# propensity, q1 = w (y - g1) / e, q0 = (1 - w)(y - g0) / (1 - e),
+# a = w (y - g0) - e q0, c = -(1 - w)(y - g1) + (1 - e) q1 and psi = a + c
+TARGET_MOMENTS = ("S psi", "S psi^2", "n", "n_clipped", "S a", "S a^2", "S a w", "S c", "S c^2",
+                  "S c (1-w)", "S a c", "n_treated")
+TARGETS = ("all", "treated", "control")      # the order of every per-target list and of cov
+
+
+def check_targets(targets) -> tuple:
+    """Target populations as a tuple of distinct names from ``TARGETS``, at least one. A
+    single name is one target."""
+    if isinstance(targets, str):
+        targets = (targets,)
+    try:
+        out = tuple(targets)
+    except TypeError:
+        raise ValueError(f"targets must be a sequence of names from {TARGETS}") from None
+    if not out:
+        raise ValueError(f"at least one target of {TARGETS} is needed")
+    for t in out:
+        if t not in TARGETS:
+            raise ValueError(f"unknown target {t!r}: pick from {TARGETS}")
+    if len(set(out)) != len(out):
+        raise ValueError(f"targets must be distinct, got {out}")
+    return out
+
+
+def target_estimates(mom):
+    """(theta [3], cov [3][3]) in the order of ``TARGETS`` from the 12 moments, float64 on the
+    host. With n1 = n_treated, n0 = n - n1, p1 = n1 / n, p0 = n0 / n:
+
+        theta_all = S psi / n      theta_treated = S a / n1      theta_control = S c / n0
+        phi_all = psi - theta_all
+        phi_trt = (a - theta_treated w) / p1         (the ATTE score of DoubleML's IRM)
+        phi_ctl = (c - theta_control (1 - w)) / p0
+        cov[j][k] = S phi_j phi_k / (n - 1) / n      (the n - 1 rule of irm.mean_se)
+
+    in closed form: S psi a = S a^2 + S a c, S psi c = S c^2 + S a c, S a (1 - w) = S a -
+    S a w, S c w = S c - S c (1 - w), w (1 - w) = 0, and phi_trt and phi_ctl sum to 0.
+    cov[0][0] has the operation order of ``estimators.irm.irm_finalize``."""
+    m = [float(v) for v in mom]
+    if len(m) != len(TARGET_MOMENTS):
+        raise ValueError(f"{len(TARGET_MOMENTS)} moments expected, got {len(m)}")
+    s_psi, s_psi2, n, _, s_a, s_a2, s_aw, s_c, s_c2, s_cv, s_ac, n1 = m
+    nan = float("nan")
+    n0 = n - n1
+    if not (math.isfinite(n) and n > 1 and 0 < n1 < n):
+        return [nan] * 3, [[nan] * 3 for _ in range(3)]
+    p1, p0 = n1 / n, n0 / n
+    th, t1, t0 = s_psi / n, s_a / n1, s_c / n0
+    ss = [[0.0] * 3 for _ in range(3)]
+    ss[0][0] = s_psi2 - s_psi * s_psi / n
+    ss[1][1] = (s_a2 - 2.0 * t1 * s_aw + t1 * t1 * n1) / (p1 * p1)
+    ss[2][2] = (s_c2 - 2.0 * t0 * s_cv + t0 * t0 * n0) / (p0 * p0)
+    ss[0][1] = (s_a2 + s_ac - t1 * (s_aw + (s_c - s_cv))) / p1
+    ss[0][2] = (s_c2 + s_ac - t0 * ((s_a - s_aw) + s_cv)) / p0
+    ss[1][2] = (s_ac - t0 * (s_a - s_aw) - t1 * (s_c - s_cv)) / (p1 * p0)
+    cov = [[0.0] * 3 for _ in range(3)]
+    for j in range(3):
+        for k in range(j, 3):
+            v = ss[j][k] / (n - 1) / n
+            cov[j][k] = cov[k][j] = max(v, 0.0) if j == k else v
+    return [th, t1, t0], cov
+
+
+@dataclass
+class TargetContrast:
+    """The difference ``a`` minus ``b`` of two target populations' effects, with its SE from
+    the joint covariance, the 1.96 SE bounds and the two-sided normal p-value of no
+    difference."""
+    a: str
+    b: str
+    diff: float
+    se: float
+    lower_ci: float
+    upper_ci: float
+    p_value: float
+
+
+@dataclass
+class TargetResult:
+    """The average effect of the cross-fitted interactive model over three target
+    populations -- everyone ("all", the ATE), the treated ("treated", the ATT; DoubleML
+    IRM(score="ATTE"), grf ``target.sample = "treated"``) and the controls ("control", the
+    ATC) -- with their joint covariance. Everything is a function of ``moments``
+    (TARGET_MOMENTS). A target that was not requested has NaN in its row and in its row and
+    column of ``cov``: its nuisances were not fitted."""
+    method: str
+    moments: list
+    targets: tuple                 # the requested targets, in the order of TARGETS
+    estimates: dict                # target -> AteResult, all three keys
+    cov: list                      # [3][3] in the order all, treated, control
+    diagnostics: dict = field(default_factory=dict)
+
+    @classmethod
+    def from_moments(cls, method, mom, targets=TARGETS, **diag):
+        mom = [float(v) for v in mom]
+        return cls.from_estimates(method, *target_estimates(mom), targets, moments=mom, **diag)
+
+    @classmethod
+    def from_estimates(cls, method, theta, cov, targets=TARGETS, moments=(), **diag):
+        """From (theta [3], cov [3][3]) in the order of TARGETS (the row-by-row reference)."""
+        req = check_targets(targets)
+        nan = float("nan")
+        on = [t in req for t in TARGETS]
+        theta = [float(v) if k else nan for v, k in zip(theta, on)]
+        cov = [[float(cov[j][k]) if on[j] and on[k] else nan for k in range(3)] for j in range(3)]
+        est = {}
+        for j, t in enumerate(TARGETS):
+            se = math.sqrt(cov[j][j]) if cov[j][j] >= 0.0 else nan
+            est[t] = AteResult(f"{method}: {t}", theta[j], se, theta[j] - Z * se, theta[j] + Z * se)
+        return cls(method, [float(v) for v in moments], tuple(t for t in TARGETS if t in req),
+                   est, cov, diag)
+
+    def __getitem__(self, target) -> AteResult:
+        return self.estimates[target]
+
+    def contrast(self, a="treated", b="control") -> TargetContrast:
+        """The effect on ``a`` minus the effect on ``b`` (no GPU work): "does the effect on
+        the treated differ from the effect on the controls?" is ``contrast().p_value``."""
+        for t in (a, b):
+            if t not in TARGETS:
+                raise ValueError(f"unknown target {t!r}: pick from {TARGETS}")
+        if a == b:
+            raise ValueError("a contrast needs two different targets")
+        j, k = TARGETS.index(a), TARGETS.index(b)
+        d = self.estimates[a].ate - self.estimates[b].ate
+        var = self.cov[j][j] + self.cov[k][k] - 2.0 * self.cov[j][k]
+        se = math.sqrt(max(var, 0.0)) if var == var else float("nan")
+        from statistics import NormalDist
+        pv = 2.0 * (1.0 - NormalDist().cdf(abs(d) / se)) if se > 0.0 else float("nan")
+        return TargetContrast(a, b, d, se, d - Z * se, d + Z * se, pv)
+
+    def rows(self):
+        return [{"target": t, "ATE": r.ate, "se": r.se, "lower_ci": r.lower_ci,
+                 "upper_ci": r.upper_ci} for t, r in self.estimates.items()]
+
+    def table(self) -> str:
+        d = self.diagnostics
+        lines = [f"{self.method}: n {d.get('n', '?')}, treated {d.get('n_treated', '?')}, "
+                 f"clipped {d.get('n_clipped', '?')}",
+                 f"{'target':>12s} {'effect':>9s} {'SE':>9s} {'lower_ci':>9s} {'upper_ci':>9s}"]
+        for r in self.rows():
+            lines.append(f"{r['target']:>12s} {r['ATE']:9.4f} {r['se']:9.4f} "
+                         f"{r['lower_ci']:9.4f} {r['upper_ci']:9.4f}")
+        if "treated" in self.targets and "control" in self.targets:
+            c = self.contrast()
+            lines.append(f"{'trt - ctl':>12s} {c.diff:9.4f} {c.se:9.4f} {c.lower_ci:9.4f} "
+                         f"{c.upper_ci:9.4f}  p = {c.p_value:.4g}")
+        return "\n".join(lines)
+
+    def to_json(self):
+        keep = lambda d: {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v))
+                          for k, v in d.items()}
+        return json.dumps({"method": self.method, "targets": list(self.targets),
+                           "estimates": self.rows(), "cov": self.cov, "moments": self.moments,
+                           "diagnostics": keep(self.diagnostics)})
+
+
 def results_frame(results):
     import pandas as pd
     return pd.DataFrame([r.row() for r in results])

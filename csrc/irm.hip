@@ -12,7 +12,15 @@
 // are accumulated in fp64: no per-row value is written to HBM (ate_irm_score_moments), or,
 // by the same kernels instantiated with ROWS, psi_i itself is written per row for the group
 // bootstrap of csrc/gate.hip (ate_irm_scores), or, instantiated with SENS, the 14 moments of
-// the sensitivity analysis are accumulated (ate_irm_sens_moments). w is read from the panel
+// the sensitivity analysis are accumulated (ate_irm_sens_moments), or, instantiated with
+// TARGETS, the 12 moments of the three target populations (ate_irm_target_moments): with
+//   q1 = w (y - g1) / e,  q0 = (1 - w)(y - g0) / (1 - e)      (the two quotients of psi)
+//   a  = w (y - g0) - e q0            the numerator of the effect on the treated (ATT)
+//   c  = -(1 - w)(y - g1) + (1 - e) q1   the numerator of the effect on the controls (ATC)
+// psi = a + c algebraically, theta_all = S psi / n, theta_treated = S a / n1, theta_control =
+// S c / n0, and the joint 3x3 covariance follows from
+//   {S psi, S psi^2, n, n_clipped, S a, S a^2, S a w, S c, S c^2, S c (1 - w), S a c, n_treated}
+// (result.TARGET_MOMENTS; the score of DoubleML's IRM(score="ATTE")). w is read from the panel
 // on every row, never inferred from the segment. Only the columns in the union of the three
 // LASSO supports are read, once each; the coefficient triple is staged in LDS. y / w are
 // rebuilt from their hi + lo bf16 columns on bf16 panels. Structure as csrc/dml.hip.
@@ -22,13 +30,15 @@ using namespace ate;
 
 namespace {
 
-// What a score pass produces: the 8 moments above, psi per row, or the 14 moments of the
-// sensitivity analysis (ate_irm_sens_moments below).
-enum Mode { MOMENTS = 0, ROWS = 1, SENS = 2 };
+// What a score pass produces: the 8 moments above, psi per row, the 14 moments of the
+// sensitivity analysis (ate_irm_sens_moments below) or the 12 moments of the target
+// populations (ate_irm_target_moments below).
+enum Mode { MOMENTS = 0, ROWS = 1, SENS = 2, TARGETS = 3 };
 
 constexpr int NM = 8;    // moments of MOMENTS
 constexpr int NS = 14;   // moments of SENS
-template <int MODE> constexpr int nmom() { return MODE == SENS ? NS : NM; }
+constexpr int NT = 12;   // moments of TARGETS
+template <int MODE> constexpr int nmom() { return MODE == SENS ? NS : MODE == TARGETS ? NT : NM; }
 
 template <typename T>
 __device__ __forceinline__ double ld_col(const T* X, int64_t ld, int c, int64_t i) {
@@ -126,6 +136,37 @@ __device__ __forceinline__ void irm_accumulate(double (&v)[NS], double y, double
   v[13] += w;
 }
 
+// one valid row's contribution to the 12 moments of the target populations (all, treated,
+// controls; the header comment):
+//   {S psi, S psi^2, n, n_clipped, S a, S a^2, S a w, S c, S c^2, S c (1 - w), S a c, n_treated}
+// psi, psi^2, n, n_clipped and n_treated as irm_accumulate(double (&)[NM], ...), term for
+// term: psi goes through irm_psi. No division beside the two of psi: q1 and q0 are the
+// quotients irm_psi forms (the same expressions on the same operands, one evaluation), and a
+// and c are products and differences of them.
+__device__ __forceinline__ void irm_accumulate(double (&v)[NT], double y, double w, double g0,
+                                               double g1, double m, double clip) {
+  const double lo = clip, hi = 1.0 - clip;
+  const double e = m < lo ? lo : (m > hi ? hi : m);
+  const double r1 = y - g1, r0 = y - g0;
+  const double psi = irm_psi(y, w, g0, g1, m, clip);
+  ATE_DASSERT(w == 0.0 || w == 1.0);                    // a and c: a binary treatment only
+  const double q1 = w * r1 / e, q0 = (1.0 - w) * r0 / (1.0 - e);
+  const double a = w * r0 - e * q0;
+  const double c = -(1.0 - w) * r1 + (1.0 - e) * q1;
+  v[0] += psi;
+  v[1] += psi * psi;
+  v[2] += 1.0;
+  v[3] += (m < lo || m > hi) ? 1.0 : 0.0;
+  v[4] += a;
+  v[5] += a * a;
+  v[6] += a * w;
+  v[7] += c;
+  v[8] += c * c;
+  v[9] += c * (1.0 - w);
+  v[10] += a * c;
+  v[11] += w;
+}
+
 template <int N>
 __device__ __forceinline__ void write_partial(double (&v)[N], double* red, double* partial) {
   block_sum<N>(v, red);
@@ -138,7 +179,8 @@ __device__ __forceinline__ void write_partial(double (&v)[N], double* red, doubl
 
 // fp32 / fp64 column-major panels: fp64 dot products, RPT rows per thread 256 apart.
 // MODE ROWS: `partial` is psi[ld] instead -- every row of the segment gets its score (0 on a
-// padding row) and no moment is accumulated (ate_irm_scores). SENS: the 14 moments.
+// padding row) and no moment is accumulated (ate_irm_scores). SENS: the 14 moments; TARGETS:
+// the 12 moments.
 template <typename T, int RPT, int MODE>
 __global__ __launch_bounds__(256) void irm_score_kernel(
     const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p, int P,
@@ -151,7 +193,8 @@ __global__ __launch_bounds__(256) void irm_score_kernel(
   double* cm = sh + 2 * (p + 1);        // [p+1]
   int* xc = (int*)(sh + 3 * (p + 1));   // [p]
   constexpr int N = nmom<MODE>();
-  __shared__ double red[16 * N];        // static LDS: 1024 (SENS: 1792) + 64 bytes
+  __shared__ double red[16 * N];        // static LDS: 1024 (SENS: 1792, TARGETS: 1536) + 64
+                                        // bytes, inside the 2048 irm_pass leaves free
   __shared__ int wcnt[16];
   const int s = blockIdx.y, k = s / spf;
   ATE_DASSERT(s < nseg && spf >= 1 && y0 >= 0 && w0 >= 0 && vcol >= 0);
@@ -320,8 +363,8 @@ int irm_score_t(const void* X, int64_t ld, const void* xcols, int p, int P, cons
 }
 
 // The score pass of every entry point (argument checks and the launch): ROWS writes psi[ld]
-// through `out`, otherwise `out` is the partial buffer [nseg*nbx][8] (SENS: [14]) of the
-// moment pass.
+// through `out`, otherwise `out` is the partial buffer [nseg*nbx][8] (SENS: [14], TARGETS:
+// [12]) of the moment pass.
 template <int MODE>
 int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols, int p,
              const void* segs, int nseg, int segs_per_fold, const void* coef, int y0, int y1,
@@ -337,7 +380,10 @@ int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols
   if (!(clip >= 0.0 && clip < 0.5)) return -1;
   const size_t esz = dtype == 3 ? sizeof(float) : sizeof(double);
   const size_t sh = (size_t)3 * (p + 1) * esz + (size_t)p * sizeof(int);
-  if (sh > 64 * 1024 - 2048) return -1;     // dynamic + static LDS within the 64 KB default
+  // dynamic + static LDS within the 64 KB default: the static part is 16 N 8 + 64 bytes, at
+  // most 1856 (SENS, N = 14; TARGETS, N = 12: 1600)
+  static_assert(16 * nmom<MODE>() * sizeof(double) + 64 <= 2048, "static LDS of the pass");
+  if (sh > 64 * 1024 - 2048) return -1;
   if (dtype == 1)
     return irm_score_t<float, MODE>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
                                     w0, w1, vcol, clip, nbx, out, sh, s);
@@ -713,6 +759,28 @@ ATE_API int ate_irm_sens_moments(int dtype, const void* X, int64_t cs, int64_t b
                                 y1, w0, w1, vcol, clip, nbx, partial, s);
   if (rc != 0) return rc;
   ATE_LAUNCH(irm_sum_kernel<NS>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
+             (double*)moments);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The pass of ate_irm_score_moments -- same arguments and checks, same column reads, dot
+// products and psi -- accumulating the 12 moments of the target populations (irm_accumulate
+// above; result.TARGET_MOMENTS): the average effect over all rows, on the treated and on the
+// controls with their joint covariance. partial: [nseg*nbx][12]; moments: [12]. For the same
+// nbx, moments 0-3 and 11 carry the bits of moments 0-3 and 7 of ate_irm_score_moments (same
+// per-thread order, same reduction shape). An all-zero coefficient row (a nuisance the
+// requested targets do not need) adds no column to the support.
+ATE_API int ate_irm_target_moments(int dtype, const void* X, int64_t cs, int64_t bs,
+                                   const void* xcols, int p, const void* segs, int nseg,
+                                   int segs_per_fold, const void* coef, int y0, int y1, int w0,
+                                   int w1, int vcol, double clip, int nbx, void* partial,
+                                   void* moments, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = irm_pass<TARGETS>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef,
+                                   y0, y1, w0, w1, vcol, clip, nbx, partial, s);
+  if (rc != 0) return rc;
+  ATE_LAUNCH(irm_sum_kernel<NT>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
              (double*)moments);
   ATE_CHECK_LAUNCH();
   return 0;

@@ -16,7 +16,17 @@ same rows: one captured repeated call and S captured single calls, alternated. W
 ``--score-only``: after one repeated fit, the fused multi-split score pass
 (``irm_score_multi*`` kernels) and S launches of ``ate_irm_score_moments`` on the same panel
 and coefficients, for the kernel trace; the JSON line carries each side's unique bytes.
-Recorded in profiles/irm_repeated/README.md."""
+Recorded in profiles/irm_repeated/README.md.
+
+``--targets T,T,...``: the target populations (``estimators/targets.py``) beside the plain ATE
+on the same arm-split panel: one captured ``target_phases`` call (only the nuisances the
+targets need) and one captured ``irm_phases`` call, alternated; then, on the coefficients of
+one full fit, the 12-moment pass (``ate_irm_target_moments``) and the 8-moment pass
+(``ate_irm_score_moments``), alternated in batches of ``--pass-batch`` back-to-back launches
+between two device events (one launch is ~0.1 ms: too short a window on its own). With
+``--score-only``: after one full fit, 5 launches of each pass, alternated, for a separate
+``rocprofv3 --kernel-trace --stats`` run (the two instantiations are told apart by their
+template argument: 0 = the 8 moments, 3 = the 12). Recorded in profiles/irm_targets/README.md."""
 import argparse
 import json
 import os
@@ -40,6 +50,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--score-only", action="store_true")
     ap.add_argument("--repeats", type=int, default=0, help="S > 0: time repeated cross-fitting")
+    ap.add_argument("--targets", default=None, metavar="T,T,...",
+                    help="time the target populations (all, treated, control) beside the ATE")
+    ap.add_argument("--pass-batch", type=int, default=20,
+                    help="--targets: back-to-back launches per timed sample of a score pass")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -54,6 +68,8 @@ def main():
     kw = dict(p=a.p, folds=K, seed=a.seed, dtype=a.dtype, device=dev, blocked=blocked, dgp=a.dgp)
     if a.repeats > 0:
         return repeated(a, n, K, kw)
+    if a.targets is not None:
+        return targets(a, n, K, kw)
     split = synthetic_panel(n, arm_split=True, **kw)
     torch.cuda.synchronize()
 
@@ -177,6 +193,86 @@ def repeated(a, n, K, kw):
     st = rep()
     out["res"], out["splits"] = st["res"].cpu().tolist(), st["splits"].cpu().tolist()
     out["single_res"] = one()["res"].cpu().tolist()
+    print(json.dumps(out))
+
+
+def targets(a, n, K, kw):
+    import torch
+    from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
+    from ate_replication_causalml_amd.estimators import irm as DI
+    from ate_replication_causalml_amd.estimators import targets as DT
+    from ate_replication_causalml_amd.ops.gram import plan_slot
+    from ate_replication_causalml_amd.result import TargetResult, check_targets
+    from ate_replication_causalml_amd.utils.graphs import SegmentedStep
+    tg = check_targets([t for t in a.targets.split(",") if t])
+    split = synthetic_panel(n, arm_split=True, **kw)
+    torch.cuda.synchronize()
+    if a.score_only:
+        coef = DI.run_phases(DI.irm_phases(split, K, "min", a.clip))["coef"]
+        torch.cuda.synchronize()
+        for _ in range(5):                        # alternate: both see the same clocks
+            m8 = DI.irm_score_moments(split, coef, a.clip, 2)
+            m12 = DI.irm_target_moments(split, coef, a.clip, 2)
+        torch.cuda.synchronize()
+        print(json.dumps({"mode": "score-only", "n": n, "p": a.p, "launches_each": 5,
+                          "union_support": (coef[:, :, 1:] != 0).any(1).sum(1).cpu().tolist(),
+                          "shared_bits": bool(torch.equal(m12[[0, 1, 2, 3, 11]],
+                                                          m8[[0, 1, 2, 3, 7]])),
+                          "mom8": m8.cpu().tolist(), "mom12": m12.cpu().tolist()}))
+        return
+    with plan_slot(0):
+        ate = SegmentedStep(DI.irm_phases(split, K, "min", a.clip), graph=True, warmup=1)
+    with plan_slot(1):
+        tar = SegmentedStep(DT.target_phases(split, K, tg, "min", a.clip), graph=True, warmup=1)
+    for _ in range(a.warmup):
+        ate()
+        tar()
+    torch.cuda.synchronize()
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = f()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    ms = {"irm_call": [], "targets_call": [], "pass8": [], "pass12": []}
+    for _ in range(a.calls):                      # alternate: both see the same clocks
+        ms["irm_call"].append(timed(ate)[0])
+        ms["targets_call"].append(timed(tar)[0])
+    coef = ate()["coef"].clone()                  # every nuisance: both passes read the same columns
+    torch.cuda.synchronize()
+    for _ in range(a.warmup):
+        DI.irm_score_moments(split, coef, a.clip, 2)
+        DI.irm_target_moments(split, coef, a.clip, 2)
+    torch.cuda.synchronize()
+    nb = max(a.pass_batch, 1)
+
+    def batch(f):
+        def g():
+            for _ in range(nb):
+                out = f(split, coef, a.clip, 2)
+            return out
+        return g
+
+    for _ in range(a.calls):                      # per launch: a batch's time over its size
+        t8, m8 = timed(batch(DI.irm_score_moments))
+        t12, m12 = timed(batch(DI.irm_target_moments))
+        ms["pass8"].append(t8 / nb)
+        ms["pass12"].append(t12 / nb)
+    out = {"n": n, "p": a.p, "folds": K, "dtype": a.dtype, "blocked": kw["blocked"],
+           "dgp": a.dgp, "targets": list(tg), "nuisances": list(DT.target_nuisances(tg)),
+           "calls": a.calls, "pass_batch": nb, "graphed": [ate.graphed, tar.graphed]}
+    for name, v in ms.items():
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "mean_ms": statistics.fmean(v)}
+    out["ratio_targets_over_irm_call"] = out["targets_call"]["median_ms"] / out["irm_call"]["median_ms"]
+    out["ratio_pass12_over_pass8"] = out["pass12"]["median_ms"] / out["pass8"]["median_ms"]
+    out["shared_bits"] = bool(torch.equal(m12[[0, 1, 2, 3, 11]], m8[[0, 1, 2, 3, 7]]))
+    r = TargetResult.from_moments("targets", tar()["mom"].cpu().numpy(), tg)
+    out["estimates"] = r.rows()
+    out["irm_res"] = ate()["res"].cpu().tolist()
     print(json.dumps(out))
 
 
