@@ -31,15 +31,18 @@ def _stream():
 class EnetCvResult:
     lambdas: torch.Tensor     # [nfull, L] original scale (NaN beyond nlam)
     nlam: torch.Tensor        # [nfull]
-    cvm: torch.Tensor         # [nfull, L]
-    cvsd: torch.Tensor
+    cvm: torch.Tensor         # [nfull, L] (NaN beyond nlam, on the device as on the CPU)
+    cvsd: torch.Tensor        # [nfull, L] (NaN beyond nlam)
     sel: torch.Tensor         # [nfull, 2] (idx_min, idx_1se)
-    coef_path: torch.Tensor   # [nfull, L, p+1] original-scale (intercept first)
+    coef_path: torch.Tensor   # [nfull, L, p+1] original-scale, intercept first (NaN rows
+                              # beyond nlam)
     coef_min: torch.Tensor    # [nfull, p+1]
     coef_1se: torch.Tensor    # [nfull, p+1]
     full_keys: list           # (full set index, y index) per full problem
     npass: torch.Tensor       # [nfull] passes of the full-data problems
     fold_npass: torch.Tensor | None = None   # [nfold] (< 0: the fold's wait timed out)
+    fold_nlam: torch.Tensor | None = None    # [nfold] lambdas each fold path kept (its source's
+                                             # count: what it ran ahead of the source is dropped)
 
     def check(self):
         """Raise NumericalError if any fold path was truncated (host sync). The device
@@ -267,7 +270,7 @@ def _cv_gpu(G, P, nseg, masks, xcols, ycols, p, ny, vp, one, full_probs, fold_pr
     _native.call("ate_enet_pick", coef.data_ptr(), sel.data_ptr(), p, L, nf, cmin.data_ptr(),
                  c1se.data_ptr(), fold_npass.data_ptr(), nq - nf, s)
     return EnetCvResult(lams[:nf], nlam[:nf], cvm, cvsd, sel, coef[:nf], cmin, c1se, full_keys,
-                        npass[:nf], fold_npass)
+                        npass[:nf], fold_npass, nlam[nf:])
 
 
 def _cv_cpu(G, masks, xcols, ycols, p, ny, vp, one, full_probs, fold_probs, fold_ycol, fold_holds,
@@ -345,4 +348,5 @@ def _cv_cpu(G, masks, xcols, ycols, p, ny, vp, one, full_probs, fold_probs, fold
     c1se = np.stack([coef[f, sel[f, 1]] for f in range(nf)])
     t = torch.from_numpy
     return EnetCvResult(t(lams), t(nlam), t(cvm), t(cvsd), t(sel), t(coef), t(cmin), t(c1se),
-                        full_keys, t(np.array([pth.npasses for pth in full])))
+                        full_keys, t(np.array([pth.npasses for pth in full])),
+                        fold_nlam=t(np.array([len(pth.lambdas) for pth in folds], dtype=np.int32)))

@@ -22,10 +22,10 @@ from .panel import dtype_code
 class LognetCvResult:
     lambdas: torch.Tensor    # [L] (NaN beyond nlam)
     nlam: torch.Tensor       # [1] int32
-    cvm: torch.Tensor        # [L]
-    cvsd: torch.Tensor
+    cvm: torch.Tensor        # [L] (NaN beyond nlam, on the device as on the CPU)
+    cvsd: torch.Tensor       # [L] (NaN beyond nlam)
     sel: torch.Tensor        # [2] (idx_min, idx_1se)
-    coef_path: torch.Tensor  # [L, p+1] original scale, intercept first
+    coef_path: torch.Tensor  # [L, p+1] original scale, intercept first (NaN rows beyond nlam)
     coef_min: torch.Tensor   # [p+1]
     coef_1se: torch.Tensor
     npass: torch.Tensor      # [1 + K]: full fit, then the K fold fits (< 0: wait timed out)
@@ -122,6 +122,9 @@ def cv_lognet(panel, xcols, ycol, penalty_factor=None, alpha=1.0, nlambda=100,
                  nlam.data_ptr(), L, cvm.data_ptr(), cvsd.data_ptr(), sel.data_ptr(), None, 0,
                  s)
     coef = torch.cat([a0[0][:, None], beta[0]], 1)
+    # rows the path never reached are NaN, as in the CPU twin (device-side, no host sync)
+    past = torch.arange(L, device=dev)[:, None] >= nlam[0]
+    coef = torch.where(past, torch.full((), float("nan"), **f64), coef)
     sl = sel[0].long()
     from .enet import poison_if_truncated
     cvm0, cvsd0, cmin, c1se = poison_if_truncated(npass[1:], cvm[0], cvsd[0], coef[sl[0]],

@@ -1838,7 +1838,8 @@ ATE_API int ate_enet_cvloss_gauss(const void* G, int P, const void* hold, const 
 // ------------------------------------------------------------------ selection (cv.glmnet rules)
 // For full problem f with K fold problems fold_probs[f*K + k] and fold sizes nfold[f*K+k]:
 // cvm = weighted mean, cvsd = sqrt(weighted var/(K-1)); idx_min = first (largest lambda)
-// attaining min cvm; idx_1se = first with cvm <= cvm[min] + cvsd[min].
+// attaining min cvm; idx_1se = first with cvm <= cvm[min] + cvsd[min]. cvm / cvsd are NaN
+// on [nlam, L).
 // One wave per full problem; lanes own lambdas m = lane + 64 c (c < 4, L <= 256) with the
 // per-lambda arithmetic of a serial scan, then wave reductions pick the first indices.
 // fnp[0 .. nfp): the launch's fold-problem pass counts; any < 0 (a fold path that timed out
@@ -1878,7 +1879,14 @@ __global__ __launch_bounds__(64) void cv_select_kernel(
     const int m = c * 64 + lane;
     mus[c] = INFINITY;
     sds[c] = 0.0;
-    if (m >= nl) continue;
+    if (m >= nl) {
+      // beyond the path's end: NaN like lambdas / coef (the outputs are not pre-filled)
+      if (m < L) {
+        cvm[(int64_t)f * L + m] = NAN;
+        cvsd[(int64_t)f * L + m] = NAN;
+      }
+      continue;
+    }
     double mu = 0.0;
     for (int k = 0; k < K; ++k) mu += nfold[f * K + k] * cvraw[(int64_t)fold_probs[f * K + k] * L + m];
     mu /= wsum;
