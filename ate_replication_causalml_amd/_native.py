@@ -104,6 +104,7 @@ _SIGS = {
     "ate_irm_scores": "ipllpipiipiiiiidipp",
     "ate_irm_sens_moments": "ipllpipiipiiiiidippp",
     "ate_irm_target_moments": "ipllpipiipiiiiidippp",
+    "ate_iivm_moments": "ipllpipiipiiiiiiidippp",
     "ate_group_boot": "pppliiuippp",
     "ate_group_boot_scratch": "iii",
     "ate_cate_moments": "ppplpiiippp",

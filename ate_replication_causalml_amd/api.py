@@ -26,7 +26,8 @@ policytree does) -> ate_dml_irm_policy;
 its sensitivity to unobserved confounding (DoubleML sensitivity_analysis /
 sensitivity_benchmark) -> ate_dml_irm_sensitivity;
 its effect on the treated and on the controls with the joint covariance (DoubleML
-IRM(score="ATTE"), grf average_treatment_effect(target.sample=)) -> ate_dml_irm_targets.
+IRM(score="ATTE"), grf average_treatment_effect(target.sample=)) -> ate_dml_irm_targets;
+the LATE with a binary instrument under noncompliance (DoubleML DoubleMLIIVM) -> ate_dml_iivm.
 """
 from __future__ import annotations
 
@@ -36,8 +37,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import (AteResult, CateResult, GateResult, PolicyTreeResult, SensitivityResult, TargetResult,
-                     format_table, results_frame)
+from .result import (AteResult, CateResult, GateResult, LateResult, PolicyTreeResult, SensitivityResult,
+                     TargetResult, format_table, results_frame)
 from .utils import guards
 from .utils.tracing import trace
 
@@ -381,6 +382,31 @@ def ate_dml_irm_targets(Y, W, X, targets=("all", "treated", "control"), folds=5,
                                   dtype=run.dtype, repeats=repeats)
 
 
+def ate_dml_iivm(Y, W, Z, X, folds=5, lambda_rule="min", clip=0.01, always_takers=True,
+                 never_takers=True, run=None) -> LateResult:
+    """The local average treatment effect (LATE) of the cross-fitted interactive IV model
+    (DoubleML DoubleMLIIVM) with CV-LASSO nuisances: the effect of the treatment taken W on
+    those whose take-up follows the binary instrument Z (the treatment assigned, e.g. an
+    encouragement). The result carries the LATE, the ITT (the ate_dml_irm effect of Z on Y),
+    the first stage with its t statistic, their covariance and the weak-instrument-robust
+    ``result.anderson_rubin()`` set (estimators/late.py). W and Z must be binary.
+    always_takers / never_takers: set False under one-sided noncompliance (DoubleML
+    ``subgroups``); that nuisance is then fixed instead of fitted. Repeated cross-fitting,
+    group / curve / policy / sensitivity versions and non-binary instruments are not
+    available."""
+    run = _run(run)
+    with trace("ate_dml_iivm", folds=folds):
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_iivm_lasso(Y, W, Z, X, folds=folds, seed=run.seed,
+                                    lambda_rule=lambda_rule, clip=clip,
+                                    always_takers=always_takers, never_takers=never_takers)
+        from .estimators import late as DL
+        return DL.dml_iivm_lasso(Y, W, Z, X, folds=folds, seed=run.seed, lambda_rule=lambda_rule,
+                                 clip=clip, always_takers=always_takers,
+                                 never_takers=never_takers, device=run.device(), dtype=run.dtype)
+
+
 def ate_residual_balance(Y, W, X, balance: BalanceConfig | None = None,
                          method="residual_balancing", run=None) -> AteResult:
     """E14 residual_balance_ATE (ate_functions.R:393-405) -> balanceHD::residualBalance.ate."""
@@ -554,7 +580,7 @@ def replicate(data=None, config: ReplicateConfig | None = None, log_path=None, p
 __all__ = [
     "ate_naive", "ate_ols", "propensity_logistic", "propensity_lasso", "ate_ipw", "ate_ipw_wls",
     "ate_lasso_single", "ate_lasso", "ate_aipw_rf", "ate_aipw_glm", "ate_belloni",
-    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_policy", "ate_dml_irm_sensitivity", "ate_dml_irm_targets", "ate_residual_balance", "ate_causal_forest", "replicate",
+    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_policy", "ate_dml_irm_sensitivity", "ate_dml_irm_targets", "ate_dml_iivm", "ate_residual_balance", "ate_causal_forest", "replicate",
     "ate_aipw_crossfit", "ate_causal_forest_bootstrap",
-    "Replication", "AteResult", "CateResult", "GateResult", "PolicyTreeResult", "SensitivityResult", "TargetResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
+    "Replication", "AteResult", "CateResult", "GateResult", "PolicyTreeResult", "SensitivityResult", "TargetResult", "LateResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
 ]

@@ -2,6 +2,7 @@
 
   replicate  run the 14-row driver (ate_replication.Rmd) and print/log/plot it
   dml        K-fold DML cross-fit on a synthetic N x p panel (the north-star job)
+  late       the LATE of the interactive IV model (DML-IIVM) on a synthetic encouragement design
   build      compile the gfx950 HIP library and the host C++ library
 """
 from __future__ import annotations
@@ -214,6 +215,25 @@ def _dml(a):
     return 0
 
 
+def _late(a):
+    # the LATE of the interactive IV model on the encouragement design of data.dgp
+    from .api import ate_dml_iivm
+    from .config import RunConfig
+    from .data.dgp import make_late_data
+    at, nt = not a.no_always_takers, not a.no_never_takers
+    d = make_late_data(a.n, a.seed, always_takers=at, never_takers=nt)
+    try:
+        r = ate_dml_iivm(d.Y, d.D, d.Z, d.X, folds=a.folds, lambda_rule=a.lambda_rule,
+                         clip=a.clip, always_takers=at, never_takers=nt,
+                         run=RunConfig(backend=a.backend, dtype=a.dtype, seed=a.seed))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    out = json.loads(r.json())
+    out["late_true"] = d.late_true
+    print(json.dumps(out))
+    return 0
+
+
 def _build(a):
     from . import _build as b
     b.build_all()
@@ -289,6 +309,20 @@ def main(argv=None):
                    help="irm: the effect over these target populations (all, treated, control) "
                         "with their joint covariance")
     d.set_defaults(fn=_dml)
+    l = sub.add_parser("late")
+    l.add_argument("--n", type=int, default=50_000)
+    l.add_argument("--seed", type=int, default=1991)
+    l.add_argument("--folds", type=int, default=5)
+    l.add_argument("--clip", type=float, default=0.01,
+                   help="the instrument propensity is clipped to [clip, 1 - clip]")
+    l.add_argument("--lambda-rule", default="min", choices=["min", "1se"])
+    l.add_argument("--no-always-takers", action="store_true",
+                   help="one-sided noncompliance: nobody takes the treatment unassigned (r0 = 0)")
+    l.add_argument("--no-never-takers", action="store_true",
+                   help="one-sided noncompliance: everybody assigned takes it (r1 = 1)")
+    l.add_argument("--backend", default="auto", choices=["auto", "gpu", "cpu", "reference"])
+    l.add_argument("--dtype", default="f64", choices=["f64", "f32", "bf16"])
+    l.set_defaults(fn=_late)
     b = sub.add_parser("build")
     b.set_defaults(fn=_build)
     a = ap.parse_args(argv)

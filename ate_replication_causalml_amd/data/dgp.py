@@ -197,3 +197,58 @@ def make_tutorial_data(n: int = 50_000, seed: int = 1991, p_extra: int = 0,
         names += [f"x_extra{j}" for j in range(p_extra)]
     X = np.column_stack(blocks)
     return TutorialData(X=X, W=W, Y=Y, names=names, tau_true=float(tau_i.mean()))
+
+
+S_Z = 70            # LATE data: the instrument (the treatment assigned)
+S_TYPE = 71         # LATE data: the latent compliance type
+S_YL = 72           # LATE data: the outcome
+
+
+@dataclass
+class LateData:
+    X: np.ndarray          # (n, p) float64, the tutorial's covariates
+    Y: np.ndarray          # (n,) float64 in {0,1}
+    D: np.ndarray          # (n,) float64 in {0,1}: the treatment taken
+    Z: np.ndarray          # (n,) float64 in {0,1}: the instrument (the treatment assigned)
+    names: list
+    late_true: float       # the mean effect of D on P(Y = 1) over the compliers of the sample
+    types: np.ndarray      # (n,) int8: 0 complier, 1 always-taker, 2 never-taker
+
+    @property
+    def n(self):
+        return self.X.shape[0]
+
+
+def make_late_data(n: int = 50_000, seed: int = 1991, p_extra: int = 0, always_takers=True,
+                   never_takers=True, params: DgpParams = TUTORIAL) -> LateData:
+    """An encouragement design on the tutorial's covariates (``make_tutorial_data``): a
+    mailing Z is assigned with a probability that depends on X, and the treatment taken D
+    follows it only for the compliers. With s = sigmoid:
+
+        Z ~ Bern(s(0.5 yob + 0.6 (g2002 - 0.8)))
+        type: always-taker with probability s(-1.6 + 0.5 city), never-taker with probability
+              s(-1.2 - 0.5 hh_size) (capped so the two sum to at most 1), else complier
+        D = 1 for always-takers, 0 for never-takers, Z for compliers
+        P(Y = 1) = 0.2 + 0.3 s(0.8 yob + 0.5 (g2000 - 0.85)) + tau D,
+        tau = 0.2 + 0.1 sex for compliers, 0.05 for always-takers (never-takers: D = 0)
+
+    so the effect differs by type and the LATE (the mean of tau over the compliers) is not
+    the ATE. ``always_takers=False`` / ``never_takers=False`` drop that type: one-sided
+    noncompliance. Every draw is a Philox function of (seed, stream, row)."""
+    d = make_tutorial_data(n, seed, p_extra, params)
+    X = d.X
+    col = {k: X[:, j] for j, k in enumerate(d.names)}
+    s = lambda v: 1.0 / (1.0 + np.exp(-v))
+    idx = np.arange(n, dtype=np.uint64)
+    Z = (_uniform(seed, S_Z, idx) < s(0.5 * col["yob"] + 0.6 * (col["g2002"] - 0.8))).astype(
+        np.float64)
+    p_at = s(-1.6 + 0.5 * col["city"]) if always_takers else np.zeros(n)
+    p_nt = np.minimum(s(-1.2 - 0.5 * col["hh_size"]), 1.0 - p_at) if never_takers else np.zeros(n)
+    u = _uniform(seed, S_TYPE, idx)
+    types = np.where(u < p_at, 1, np.where(u >= 1.0 - p_nt, 2, 0)).astype(np.int8)
+    D = np.where(types == 1, 1.0, np.where(types == 2, 0.0, Z))
+    tau = np.where(types == 0, 0.2 + 0.1 * col["sex"], 0.05)
+    base = 0.2 + 0.3 * s(0.8 * col["yob"] + 0.5 * (col["g2000"] - 0.85))
+    Y = (_uniform(seed, S_YL, idx) < base + tau * D).astype(np.float64)
+    return LateData(X=X, Y=Y, D=D, Z=Z, names=list(d.names), late_true=float(tau[types == 0].mean()),
+                    types=types)

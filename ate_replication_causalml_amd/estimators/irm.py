@@ -608,7 +608,7 @@ def irm_repeated_panel(pan, folds: int, repeats: int, lambda_rule="min", clip=0.
 
 # ---------------------------------------------------------------- the shared front end
 def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts=None,
-                    check_extra=None, cells=check_cells):
+                    check_extra=None, cells=check_cells, targets=None):
     """The prologue of every ``dml_irm_*`` estimator: the binary-W check, the fold ids, the
     (global) rows per (fold, arm) cell and the arm-split panel (segment 2k + a = fold k,
     W = a) on ``device``. Returns (pan, counts [2K], extra, n_total, rid).
@@ -618,7 +618,9 @@ def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts
     ``extra`` and are handed to ``check_extra`` before the panel is built. rid: the rows'
     global ids in panel row order (the key of the bootstrap multipliers), -1 on padding.
     cells: the check of the cell counts, ``cells(counts, folds)`` (repeated cross-fitting
-    passes its own: its K*K micro-groups may have an empty arm)."""
+    passes its own: its K*K micro-groups may have an empty arm). targets: further named
+    target columns of the panel (``build_panel(targets=)``; estimators/late.py: the treatment
+    taken D beside the instrument in column W)."""
     dev = resolve_device(device)
     Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
     if not np.isin(Wn, (0.0, 1.0)).all():
@@ -635,7 +637,8 @@ def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts
     if check_extra is not None:
         check_extra(extra)
     cells(counts, folds)
-    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev, nseg=2 * folds)
+    pan = build_panel(Xn, Wn, Yn, folds=seg, dtype=dtype, device=dev, nseg=2 * folds,
+                      targets=targets)
     rid = torch.where(pan.row_index >= 0,
                       pan.row_index + (dist.row_offset if dist is not None else 0),
                       torch.full_like(pan.row_index, -1))

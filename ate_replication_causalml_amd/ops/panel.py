@@ -126,13 +126,17 @@ def _round_up(x, m):
 
 
 def build_panel(X, W=None, Y=None, folds=None, dtype="f64", device="cpu", extra_cols=(),
-                col_align=None, split_hi_lo=None, nseg=None) -> DevicePanel:
+                col_align=None, split_hi_lo=None, nseg=None, targets=None) -> DevicePanel:
     """Assemble a panel from host arrays.
 
     folds: optional (n,) int fold id -> one padded segment per fold (in fold order).
     nseg: at least this many segments (default: the largest fold id + 1), so that a layout
     keeps its trailing segments when no row falls in them (they hold padding rows only).
     extra_cols: names of zero-initialised scratch columns to reserve.
+    targets: optional mapping name -> (n,) values of further target columns (the treatment
+    taken ``D`` of the IV model): placed after W / Y and their hi / lo copies and before
+    ``extra_cols``, each with its own hi + lo copies on a split panel. Absent: the layout without them,
+    byte for byte.
     X may be a torch tensor (e.g. already in HBM): its fold gather and transposition
     then run on ``device`` (no host round trip of the n x p block); same values.
     """
@@ -161,6 +165,13 @@ def build_panel(X, W=None, Y=None, folds=None, dtype="f64", device="cpu", extra_
         vecs["Y"] = np.asarray(Y, float)
     if split_hi_lo:
         for k in list(vecs):
+            names += [f"{k}_hi", f"{k}_lo"]
+    for k, v in (targets or {}).items():
+        if k in names or k in extra_cols or len(np.shape(v)) != 1 or len(v) != n:
+            raise ValueError(f"target column {k!r}: a new name and {n} values are needed")
+        names.append(k)
+        vecs[k] = np.asarray(v, float)
+        if split_hi_lo:
             names += [f"{k}_hi", f"{k}_lo"]
     names += list(extra_cols)
     P = _round_up(len(names), col_align)

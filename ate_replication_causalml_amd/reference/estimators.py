@@ -870,6 +870,80 @@ def dml_irm_targets(Y, W, X, targets=("all", "treated", "control"), folds=5, see
                                        hipgraph=False)
 
 
+def _iivm_scores(Y, D, Z, X, folds, seed, lambda_rule, clip, always_takers, never_takers,
+                 fold_ids=None):
+    """The held-out nuisances and the two per-row AIPW scores of the cross-fitted interactive
+    IV model (validated inputs as float64 arrays), in the shape of _irm_scores with the
+    instrument Z splitting the rows: (b, a, g0, g1, r0, r1, m), m before clipping. Without
+    always-takers r0 = 0, without never-takers r1 = 1: fixed, not fitted."""
+    for name, v in (("treatment W", D), ("instrument Z", Z)):
+        if not np.isin(v, (0.0, 1.0)).all():
+            raise ValueError(f"DML-IIVM needs a binary {name}: it must be exactly 0 or 1")
+    fid = rng.fold_ids(len(Y), folds, seed, stream=0) if fold_ids is None else \
+        np.asarray(fold_ids, dtype=np.int64)
+    for k in range(folds):
+        for z in (0, 1):
+            if not np.any((fid == k) & (Z == z)):
+                raise ValueError(f"empty (fold, arm) cell: fold {k}, arm W={z} has no rows")
+    for z, (flag, name) in enumerate(((always_takers, "always_takers"),
+                                      (never_takers, "never_takers"))):
+        for k in range(folds):
+            cell = D[(fid == k) & (Z == z)]
+            if not flag:
+                if np.any(cell == 1 - z):
+                    raise ValueError(f"{name}=False needs D = {z} wherever Z = {z}: fold {k} has "
+                                     f"{int((cell == 1 - z).sum())} rows with Z={z}, D={1 - z}; "
+                                     f"set {name}=True")
+                continue
+            for d in (0, 1):
+                if not np.any(cell == d):
+                    raise ValueError(f"empty (fold, Z, D) cell: fold {k}, Z={z}, D={d} has no "
+                                     f"rows, so r{z} = E[D|Z={z},X] cannot be fitted; set "
+                                     f"{name}=False if D = {z} wherever Z = {z}")
+    s = "lambda.min" if lambda_rule == "min" else "lambda.1se"
+    g0, g1, m = np.empty_like(Y), np.empty_like(Y), np.empty_like(Y)
+    r0, r1 = np.zeros_like(Y), np.ones_like(Y)
+    for k in range(folds):
+        te = fid == k
+        inner = np.where(fid > k, fid - 1, fid)
+        fits = [((~te) & (Z == 0), Y, g0), ((~te) & (Z == 1), Y, g1), (~te, Z, m)]
+        if always_takers:
+            fits.append(((~te) & (Z == 0), D, r0))
+        if never_takers:
+            fits.append(((~te) & (Z == 1), D, r1))
+        for rows, target, out in fits:
+            cv = gn.cv_glmnet(X[rows], target[rows], foldid=inner[rows])
+            out[te] = cv.predict(X[te], s=s)
+    e = np.clip(m, clip, 1 - clip)
+    b = g1 - g0 + Z * (Y - g1) / e - (1 - Z) * (Y - g0) / (1 - e)
+    a = r1 - r0 + Z * (D - r1) / e - (1 - Z) * (D - r0) / (1 - e)
+    return b, a, g0, g1, r0, r1, m
+
+
+def dml_iivm_lasso(Y, W, Z, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                   always_takers=True, never_takers=True,
+                   method="DML-IIVM cross-fit LATE (LASSO)", fold_ids=None):
+    """The LATE of the cross-fitted interactive IV model (Chernozhukov et al. 2018 §5.2,
+    DoubleML DoubleMLIIVM) with CV-LASSO nuisances, row by row in float64, the twin of
+    estimators.late.dml_iivm_lasso: W is the treatment taken, Z the binary instrument. For
+    held-out fold k, g_z and r_z are gaussian LASSO fits of Y and of W on the training rows
+    with Z = z and m is the linear-probability LASSO of Z on all training rows, each with
+    lambda chosen by (K-1)-fold CV over the training folds (as dml_irm_lasso). With b the
+    AIPW score of Y and a that of W, both split by Z over the clipped m: theta = sum(b) /
+    sum(a), SE = sd((b - theta a) / mean(a)) / sqrt(n). The 15 sums of result.LATE_MOMENTS
+    are taken over the per-row arrays here."""
+    from ..result import LateResult
+    Y, D, Z, X = _arr(Y), _arr(W), _arr(Z), _arr(X)
+    b, a, g0, g1, r0, r1, m = _iivm_scores(Y, D, Z, X, folds, seed, lambda_rule, clip,
+                                           bool(always_takers), bool(never_takers), fold_ids)
+    n = len(Y)
+    mom = [b.sum(), (b * b).sum(), float(n), float(((m < clip) | (m > 1 - clip)).sum()),
+           a.sum(), (a * a).sum(), (a * b).sum(), Z.sum(), (Z * D).sum(), ((1 - Z) * D).sum(),
+           (Z * (Y - g1) ** 2).sum(), ((1 - Z) * (Y - g0) ** 2).sum(),
+           (Z * (D - r1) ** 2).sum(), ((1 - Z) * (D - r0) ** 2).sum(), ((Z - m) ** 2).sum()]
+    return LateResult.from_moments(method, mom, n=n, hipgraph=False)
+
+
 def dml_plr_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="min",
                            aggregate="median", method="DML cross-fit (LASSO, repeated)"):
     """Repeated cross-fitting (Chernozhukov et al. 2018 §3.4, median method): S = repeats

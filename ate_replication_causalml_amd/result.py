@@ -769,6 +769,173 @@ class TargetResult:
                            "diagnostics": keep(self.diagnostics)})
 
 
+# ------------------------------------------------------------ LATE (interactive IV model)
+# the 15 moments of the LATE pass (estimators/late.py, csrc/iivm.hip), with e the clipped
+# instrument propensity, b the AIPW score of Y and a the AIPW score of the treatment taken D,
+# both split by the instrument z
+LATE_MOMENTS = ("S b", "S b^2", "n", "n_clipped", "S a", "S a^2", "S a b", "S z", "S z d",
+                "S (1-z) d", "S z (y-g1)^2", "S (1-z)(y-g0)^2", "S z (d-r1)^2",
+                "S (1-z)(d-r0)^2", "S (z-m)^2")
+
+
+def _mean_se(s1, s2, n):
+    """(mean, SE) by the n - 1 rule, the host form of ``estimators.irm.mean_se``."""
+    return s1 / n, math.sqrt(max((s2 - s1 * s1 / n) / (n - 1) / n, 0.0))
+
+
+def late_estimates(mom):
+    """(late, se, itt, itt_se, first_stage, first_stage_se, cov_itt_first_stage) from the 15
+    moments, float64 on the host:
+
+        theta = S b / S a
+        SE^2  = [S b^2 - 2 theta S a b + theta^2 S a^2] / (n - 1) / n / (S a / n)^2
+
+    (the influence values (b - theta a) / mean(a) sum to zero; the n - 1 rule of
+    ``irm.mean_se``), the ITT ``mean_se(S b, S b^2, n)``, the first stage ``mean_se(S a,
+    S a^2, n)`` and their covariance ``(S a b - S a S b / n) / (n - 1) / n``."""
+    m = [float(v) for v in mom]
+    if len(m) != len(LATE_MOMENTS):
+        raise ValueError(f"{len(LATE_MOMENTS)} moments expected, got {len(m)}")
+    sb, sbb, n, _, sa, saa, sab = m[:7]
+    if not (math.isfinite(n) and n > 1 and all(math.isfinite(v) for v in m[:7])):
+        return (float("nan"),) * 7
+    itt, itt_se = _mean_se(sb, sbb, n)
+    fs, fs_se = _mean_se(sa, saa, n)
+    cov = (sab - sa * sb / n) / (n - 1) / n
+    if sa == 0.0:
+        return float("nan"), float("nan"), itt, itt_se, fs, fs_se, cov
+    th = sb / sa
+    var = (sbb - 2.0 * th * sab + th * th * saa) / (n - 1) / n / (sa / n) ** 2
+    return th, math.sqrt(max(var, 0.0)), itt, itt_se, fs, fs_se, cov
+
+
+@dataclass
+class ArSet:
+    """The Anderson-Rubin confidence set of the LATE. kind "interval": [lower, upper];
+    "two_rays": (-inf, lower] and [upper, inf) (a weak first stage: one of the two may be
+    infinite when the set is a single ray); "all": the whole line (lower = -inf, upper =
+    inf)."""
+    kind: str
+    lower: float
+    upper: float
+    level: float
+
+    def __contains__(self, theta) -> bool:
+        if self.kind == "interval":
+            return self.lower <= theta <= self.upper
+        return self.kind == "all" or theta <= self.lower or theta >= self.upper
+
+
+@dataclass
+class LateResult:
+    """The local average treatment effect of the cross-fitted interactive IV model (DoubleML
+    ``DoubleMLIIVM``): the effect of the treatment taken on those whose take-up follows the
+    binary instrument. ``late`` = ITT / first stage, where ``itt`` is the AIPW effect of the
+    instrument on Y and ``first_stage`` its AIPW effect on the treatment taken (each an
+    AteResult), with their 2x2 covariance ``cov`` (order itt, first stage). Everything is a
+    function of ``moments`` (LATE_MOMENTS)."""
+    method: str
+    late: float
+    se: float
+    lower_ci: float
+    upper_ci: float
+    itt: AteResult
+    first_stage: AteResult
+    first_stage_t: float
+    cov: list
+    moments: list
+    diagnostics: dict = field(default_factory=dict)
+
+    @classmethod
+    def from_moments(cls, method, mom, **diag):
+        """From the 15 moments; the counts and held-out RMSEs of the diagnostics (n_clipped,
+        n_z1, the four compliance cells n_z{z}_d{d}, rmse_g0 .. rmse_m) come from them too,
+        ``diag`` adds n and hipgraph."""
+        mom = [float(v) for v in mom]
+        th, se, itt, itt_se, fs, fs_se, cov = late_estimates(mom)
+        n, nz1 = mom[2], mom[7]
+        nz0 = n - nz1
+        cnt = lambda x: int(round(x)) if math.isfinite(x) else -1
+        rm = lambda s, k: math.sqrt(s / k) if k > 0 and s >= 0 else float("nan")
+        d = dict(n_clipped=cnt(mom[3]), n_z1=cnt(nz1), n_z0_d0=cnt(nz0 - mom[9]),
+                 n_z0_d1=cnt(mom[9]), n_z1_d0=cnt(nz1 - mom[8]), n_z1_d1=cnt(mom[8]),
+                 rmse_g0=rm(mom[11], nz0), rmse_g1=rm(mom[10], nz1), rmse_r0=rm(mom[13], nz0),
+                 rmse_r1=rm(mom[12], nz1), rmse_m=rm(mom[14], n))
+        d.update(diag)
+        d.setdefault("n", cnt(n))
+        return cls(method, th, se, th - Z * se, th + Z * se,
+                   AteResult.make(f"{method}: ITT", itt, itt_se),
+                   AteResult.make(f"{method}: first stage", fs, fs_se),
+                   fs / fs_se if fs_se > 0 else float("nan"),
+                   [[itt_se * itt_se, cov], [cov, fs_se * fs_se]], mom, d)
+
+    def anderson_rubin(self, level=0.95) -> ArSet:
+        """The weak-instrument-robust confidence set {theta : n mean(phi)^2 / var(phi) <=
+        chi2_1(level)}, phi = b - theta a, var by the n - 1 rule. With k = chi2 / (n - 1) it
+        is the quadratic inequality A theta^2 + B theta + C <= 0,
+
+            A = (1 + k) (S a)^2 / n - k S a^2
+            B = -2 (1 + k) S a S b / n + 2 k S a b
+            C = (1 + k) (S b)^2 / n - k S b^2,
+
+        solved in closed form on the host. A > 0 (a first stage away from zero at this
+        level): an interval; A < 0: two rays, or the whole line when there is no real root.
+        theta-hat = S b / S a has mean(phi) = 0 and is always inside."""
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must be in (0, 1)")
+        sb, sbb, n, _, sa, saa, sab = self.moments[:7]
+        inf = float("inf")
+        k = normal_quantile(0.5 + level / 2.0) ** 2 / (n - 1)
+        A = (1 + k) * sa * sa / n - k * saa
+        B = -2 * (1 + k) * sa * sb / n + 2 * k * sab
+        C = (1 + k) * sb * sb / n - k * sbb
+        if A == 0.0:                                    # B theta + C <= 0
+            if B == 0.0:
+                return ArSet("all", -inf, inf, level)
+            return ArSet("two_rays", -C / B, inf, level) if B > 0 else \
+                ArSet("two_rays", -inf, -C / B, level)
+        disc = B * B - 4 * A * C
+        if disc <= 0.0 and A < 0:
+            return ArSet("all", -inf, inf, level)
+        r = math.sqrt(max(disc, 0.0))
+        # the root of larger magnitude without cancellation, the other from the product
+        q = -0.5 * (B + math.copysign(r, B))
+        roots = sorted((q / A, C / q)) if q != 0.0 else [0.0, 0.0]
+        return ArSet("interval" if A > 0 else "two_rays", roots[0], roots[1], level)
+
+    def table(self) -> str:
+        d = self.diagnostics
+        ar = self.anderson_rubin()
+        row = lambda name, r: (f"{name:>12s} {r.ate:9.4f} {r.se:9.4f} {r.lower_ci:9.4f} "
+                               f"{r.upper_ci:9.4f}")
+        shape = {"interval": f"[{ar.lower:.4f}, {ar.upper:.4f}]", "all": "the whole line",
+                 "two_rays": f"(-inf, {ar.lower:.4f}] and [{ar.upper:.4f}, inf)"}[ar.kind]
+        return "\n".join([
+            f"{self.method}: n {d.get('n', '?')}, Z=1 {d.get('n_z1', '?')}, clipped "
+            f"{d.get('n_clipped', '?')}, cells (z,d) 00 {d.get('n_z0_d0', '?')} 01 "
+            f"{d.get('n_z0_d1', '?')} 10 {d.get('n_z1_d0', '?')} 11 {d.get('n_z1_d1', '?')}",
+            f"{'':>12s} {'effect':>9s} {'SE':>9s} {'lower_ci':>9s} {'upper_ci':>9s}",
+            row("LATE", AteResult("", self.late, self.se, self.lower_ci, self.upper_ci)),
+            row("ITT", self.itt), row("first stage", self.first_stage) +
+            f"  t = {self.first_stage_t:.2f}",
+            f"Anderson-Rubin 95% set: {shape}"])
+
+    def json(self) -> str:
+        keep = lambda d: {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v))
+                          for k, v in d.items()}
+        ar = self.anderson_rubin()
+        est = lambda r: {"estimate": r.ate, "se": r.se, "lower_ci": r.lower_ci,
+                         "upper_ci": r.upper_ci}
+        return json.dumps({"method": self.method, "late": self.late, "se": self.se,
+                           "lower_ci": self.lower_ci, "upper_ci": self.upper_ci,
+                           "itt": est(self.itt), "first_stage": est(self.first_stage),
+                           "first_stage_t": self.first_stage_t, "cov": self.cov,
+                           "anderson_rubin": asdict(ar), "moments": self.moments,
+                           "diagnostics": keep(self.diagnostics)})
+
+    to_json = json
+
+
 def results_frame(results):
     import pandas as pd
     return pd.DataFrame([r.row() for r in results])

@@ -23,8 +23,10 @@
 // (result.TARGET_MOMENTS; the score of DoubleML's IRM(score="ATTE")). w is read from the panel
 // on every row, never inferred from the segment. Only the columns in the union of the three
 // LASSO supports are read, once each; the coefficient triple is staged in LDS. y / w are
-// rebuilt from their hi + lo bf16 columns on bf16 panels. Structure as csrc/dml.hip.
-#include "common.hpp"
+// rebuilt from their hi + lo bf16 columns on bf16 panels. Structure as csrc/dml.hip. What
+// the LATE pass of csrc/iivm.hip shares (ld_col, Seg, compact_support_n, irm_psi,
+// write_partial, irm_sum_kernel) lives in irm_common.hpp.
+#include "irm_common.hpp"
 
 using namespace ate;
 
@@ -39,13 +41,6 @@ constexpr int NM = 8;    // moments of MOMENTS
 constexpr int NS = 14;   // moments of SENS
 constexpr int NT = 12;   // moments of TARGETS
 template <int MODE> constexpr int nmom() { return MODE == SENS ? NS : MODE == TARGETS ? NT : NM; }
-
-template <typename T>
-__device__ __forceinline__ double ld_col(const T* X, int64_t ld, int c, int64_t i) {
-  return (double)X[(int64_t)c * ld + i];
-}
-
-struct Seg { int64_t r0, r1; };
 
 // Ordered compaction (ascending j: the dot products keep the summation order of the dense
 // loop, bit for bit) of the feature columns with a nonzero coefficient in any of the three
@@ -76,15 +71,6 @@ __device__ int compact_support3(C* c0, C* c1, C* cm, int* xc, int p, int* wcnt /
     base = tot;
   }
   return base;
-}
-
-// the AIPW score of one valid row (everything after the three dot products, fp64)
-__device__ __forceinline__ double irm_psi(double y, double w, double g0, double g1, double m,
-                                          double clip) {
-  const double lo = clip, hi = 1.0 - clip;
-  const double e = m < lo ? lo : (m > hi ? hi : m);
-  const double r1 = y - g1, r0 = y - g0;
-  return g1 - g0 + w * r1 / e - (1.0 - w) * r0 / (1.0 - e);
 }
 
 // one valid row's contribution to the 8 moments
@@ -165,16 +151,6 @@ __device__ __forceinline__ void irm_accumulate(double (&v)[NT], double y, double
   v[9] += c * (1.0 - w);
   v[10] += a * c;
   v[11] += w;
-}
-
-template <int N>
-__device__ __forceinline__ void write_partial(double (&v)[N], double* red, double* partial) {
-  block_sum<N>(v, red);
-  if (threadIdx.x == 0) {
-    double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * N;
-#pragma unroll
-    for (int q = 0; q < N; ++q) out[q] = v[q];
-  }
 }
 
 // fp32 / fp64 column-major panels: fp64 dot products, RPT rows per thread 256 apart.
@@ -334,23 +310,6 @@ __global__ __launch_bounds__(256) void irm_score_bf16_kernel(
   if (MODE != ROWS) write_partial<N>(v, red, partial);
 }
 
-// one block of 256 threads: thread i sums partials i, i+256, ... (fixed order), then a
-// fixed-shape block reduction -> deterministic for a given launch geometry (the N-moment
-// sibling of csrc/dml.hip sum7_kernel)
-template <int N>
-__global__ __launch_bounds__(256) void irm_sum_kernel(const double* __restrict__ partial, int nb,
-                                                      double* __restrict__ out) {
-  __shared__ double red[16 * N];
-  double v[N] = {};
-  for (int b = threadIdx.x; b < nb; b += 256)
-#pragma unroll
-    for (int q = 0; q < N; ++q) v[q] += partial[(int64_t)b * N + q];
-  block_sum<N>(v, red);
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int q = 0; q < N; ++q) out[q] = v[q];
-}
-
 template <typename T, int MODE>
 int irm_score_t(const void* X, int64_t ld, const void* xcols, int p, int P, const void* segs,
                 int nseg, int spf, const void* coef, int y0, int y1, int w0, int w1, int vcol,
@@ -418,43 +377,6 @@ int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols
 // ... of its split, then block_sum<8>).
 constexpr int IRM_SMAX = 4;   // splits per pass: 0 bytes of scratch and >= 2 waves / SIMD for
                               // every instantiation (profiles/irm_repeated/README.md)
-
-// compact_support3 for NV interleaved vectors: cv[(1 + j) * NV + v], xc[j]; column j stays
-// when any of its NV coefficients is nonzero. The whole block must call it.
-template <int NV, typename C>
-__device__ int compact_support_n(C* cv, int* xc, int p, int* wcnt /* [>= 16] */) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int base = 0;
-  for (int j0 = 0; j0 < p; j0 += blockDim.x) {
-    const int j = j0 + threadIdx.x;
-    C val[NV];
-    bool keep = false;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      val[v] = j < p ? cv[(int64_t)(1 + j) * NV + v] : C(0);
-      keep = keep || val[v] != C(0);
-    }
-    const int c = j < p ? xc[j] : 0;
-    const uint64_t m = __ballot(keep);
-    if (lane == 0) wcnt[wid] = __popcll(m);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wid; ++w) off += wcnt[w];
-    int tot = base;
-    for (int w = 0; w < nw; ++w) tot += wcnt[w];
-    const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();                                      // all reads of the dense slots done
-    ATE_DASSERT(pos <= j);                                // compaction only moves entries down
-    if (keep) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) cv[(int64_t)(1 + pos) * NV + v] = val[v];
-      xc[pos] = c;
-    }
-    __syncthreads();
-    base = tot;
-  }
-  return base;
-}
 
 // stage the 3 NSP coefficient vectors of segment group g (splits s0 .. s0 + NSP - 1) and the
 // column list; returns the size of the compacted union

@@ -26,7 +26,15 @@ one full fit, the 12-moment pass (``ate_irm_target_moments``) and the 8-moment p
 between two device events (one launch is ~0.1 ms: too short a window on its own). With
 ``--score-only``: after one full fit, 5 launches of each pass, alternated, for a separate
 ``rocprofv3 --kernel-trace --stats`` run (the two instantiations are told apart by their
-template argument: 0 = the 8 moments, 3 = the 12). Recorded in profiles/irm_targets/README.md."""
+template argument: 0 = the 8 moments, 3 = the 12). Recorded in profiles/irm_targets/README.md.
+
+``--iivm``: the LATE of the interactive IV model (``estimators/late.py``) beside the plain ATE
+on the same arm-split panel, whose W is taken as the instrument and whose binary covariate
+x{--iivm-col} as the treatment taken (removed from the covariates): one captured
+``late_phases`` call and one captured ``irm_phases`` call, alternated; then the 15-moment pass
+(``ate_iivm_moments``) and the 8-moment pass on the coefficients of those fits, alternated in
+batches as for ``--targets``. The JSON line carries both union sizes and the bytes each pass
+reads. Recorded in profiles/iivm/README.md."""
 import argparse
 import json
 import os
@@ -53,7 +61,11 @@ def main():
     ap.add_argument("--targets", default=None, metavar="T,T,...",
                     help="time the target populations (all, treated, control) beside the ATE")
     ap.add_argument("--pass-batch", type=int, default=20,
-                    help="--targets: back-to-back launches per timed sample of a score pass")
+                    help="--targets / --iivm: back-to-back launches per timed sample of a pass")
+    ap.add_argument("--iivm", action="store_true",
+                    help="time the LATE of the interactive IV model beside the ATE")
+    ap.add_argument("--iivm-col", type=int, default=16,
+                    help="--iivm: the exactly-binary covariate x{J} taken as the treatment D")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -70,6 +82,8 @@ def main():
         return repeated(a, n, K, kw)
     if a.targets is not None:
         return targets(a, n, K, kw)
+    if a.iivm:
+        return iivm(a, n, K, kw)
     split = synthetic_panel(n, arm_split=True, **kw)
     torch.cuda.synchronize()
 
@@ -272,6 +286,95 @@ def targets(a, n, K, kw):
     out["shared_bits"] = bool(torch.equal(m12[[0, 1, 2, 3, 11]], m8[[0, 1, 2, 3, 7]]))
     r = TargetResult.from_moments("targets", tar()["mom"].cpu().numpy(), tg)
     out["estimates"] = r.rows()
+    out["irm_res"] = ate()["res"].cpu().tolist()
+    print(json.dumps(out))
+
+
+def iivm(a, n, K, kw):
+    import dataclasses
+    import numpy as np
+    import torch
+    from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
+    from ate_replication_causalml_amd.estimators import irm as DI
+    from ate_replication_causalml_amd.estimators import late as DL
+    from ate_replication_causalml_amd.ops.gram import plan_slot
+    from ate_replication_causalml_amd.result import LateResult
+    from ate_replication_causalml_amd.utils.graphs import SegmentedStep
+    split = synthetic_panel(n, arm_split=True, **kw)
+    torch.cuda.synchronize()
+    # the panel's W is the instrument; the binary covariate x{iivm_col} (vote history, so the
+    # first stage has covariates to select) is the treatment taken and leaves the covariates.
+    # A binary column is its own hi part; its lo part is W's, which is all zero.
+    c = split.cols[f"x{a.iivm_col}"]
+    d = split.col(f"x{a.iivm_col}")
+    assert bool(((d == 0) | (d == 1)).all()), "the D column must be exactly binary"
+    cols = {**split.cols, "D": c}
+    if split.dtype == torch.bfloat16:
+        cols.update(D_hi=c, D_lo=split.cols["W_lo"])
+    pan = dataclasses.replace(split, cols=cols, xcols=[x for x in split.xcols if x != c])
+    rows = np.asarray(split.seg_nreal).reshape(K, 2).sum(1)
+
+    def nbytes(coef, ntarget):
+        # rows x (union support + target columns incl. `one`) x 2 bytes, per fold
+        nnz = (coef[:, :, 1:] != 0).any(1).sum(1).cpu().numpy()
+        return nnz.tolist(), int((rows * (nnz + ntarget) * 2).sum())
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = f()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    with plan_slot(0):
+        ate = SegmentedStep(DI.irm_phases(split, K, "min", a.clip), graph=True, warmup=1)
+    with plan_slot(1):
+        lat = SegmentedStep(DL.late_phases(pan, K, "min", a.clip), graph=True, warmup=1)
+    for _ in range(a.warmup):
+        ate()
+        lat()
+    torch.cuda.synchronize()
+    ms = {"irm_call": [], "iivm_call": [], "pass8": [], "pass15": []}
+    for _ in range(a.calls):                      # alternate: both see the same clocks
+        ms["irm_call"].append(timed(ate)[0])
+        ms["iivm_call"].append(timed(lat)[0])
+    c3, c5 = ate()["coef"].clone(), lat()["coef"].clone()
+    torch.cuda.synchronize()
+    for _ in range(a.warmup):
+        DI.irm_score_moments(split, c3, a.clip, 2)
+        DL.iivm_moments(pan, c5, a.clip, 2)
+    torch.cuda.synchronize()
+    nb = max(a.pass_batch, 1)
+
+    def batch(f, *args):
+        def g():
+            for _ in range(nb):
+                out = f(*args, a.clip, 2)
+            return out
+        return g
+
+    for _ in range(a.calls):                      # per launch: a batch's time over its size
+        t8, m8 = timed(batch(DI.irm_score_moments, split, c3))
+        t15, m15 = timed(batch(DL.iivm_moments, pan, c5))
+        ms["pass8"].append(t8 / nb)
+        ms["pass15"].append(t15 / nb)
+    out = {"n": n, "p": a.p, "folds": K, "dtype": a.dtype, "blocked": kw["blocked"],
+           "dgp": a.dgp, "iivm_col": a.iivm_col, "calls": a.calls, "pass_batch": nb,
+           "graphed": [ate.graphed, lat.graphed]}
+    for name, v in ms.items():
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "mean_ms": statistics.fmean(v)}
+    out["union8"], out["bytes8"] = nbytes(c3, 5)       # one, Y hi / lo, W hi / lo
+    out["union15"], out["bytes15"] = nbytes(c5, 7)     # and D hi / lo
+    for k, b in (("pass8", "bytes8"), ("pass15", "bytes15")):
+        out[k]["TB_per_s"] = out[b] / (out[k]["median_ms"] * 1e-3) / 1e12
+    # the moments shared with the AIPW pass on the same covariates, bit for bit
+    base = DI.irm_score_moments(pan, c5[:, [0, 1, 4]].contiguous(), a.clip, 2)
+    out["shared_bits"] = bool(torch.equal(m15[[0, 1, 2, 3, 7, 10, 11, 14]],
+                                          base[[0, 1, 2, 3, 7, 4, 5, 6]]))
+    r = LateResult.from_moments("iivm", lat()["mom"].cpu().numpy())
+    out["late"] = json.loads(r.json())
     out["irm_res"] = ate()["res"].cpu().tolist()
     print(json.dumps(out))
 
