@@ -91,12 +91,15 @@ _SIGS = {
     "ate_boot_poisson": "ppluiilipp",
     "ate_enet_isa_selftest": "pp",
     "ate_enet_prepare": "piipipiipipipppppppp",
+    "ate_enet_prepare_fused": "piipipiipipi" + "ppppppp" + "plp",
     "ate_enet_path": "pipiippppidddipppppippp",
     "ate_enet_coef": "ppiiiipppppppp",
     "ate_enet_cvloss_gauss": "pippiipppiiipp",
     "ate_cv_select": "pppiipippppip",
     "ate_enet_pick": "ppiiipppip",
+    "ate_enet_cv_tail": "pippiipppi" + "pppppp" + "iiii" + "pppppppppppp",
     "ate_dml_resid_moments": "ipllpipipiiiiiippp",
+    "ate_dml_resid_moments_final": "ipllpipipiiiiii" + "ppppp",
     "ate_dml_resid_exact": "pllpipipiiiiiiippp",
     "ate_irm_score_moments": "ipllpipiipiiiiidippp",
     "ate_irm_score_moments_multi": "ipllpipiipipiiiiiidippp",

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from ..ops import enet as enet_ops
 from ..ops import stats as S
 from ..ops.devconst import const
 from ..ops.enet import cv_enet_gaussian
@@ -416,9 +417,17 @@ def dml_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None, G
         return (cv.coef_min if lambda_rule == "min" else cv.coef_1se).reshape(
             len(mine), 2, -1).contiguous()
 
+    # world 1: the residual pass finishes its own moments and theta / SE in the same launch
+    # (csrc/dml.hip ate_dml_resid_moments_final); with a collective between the two steps
+    # (sharded, multi-rank, exact) they stay separate
+    fused_final = enet_ops.CV_FUSED and not dist and pan.data.is_cuda
+
     def phase_fit(st):
         cv = fit(st)
         coef = pick(cv)
+        if fused_final:
+            mom, res = dml_residual_moments(pan, coef, final=True)
+            return {**st, "cv": cv, "mom": mom, "res": res}
         return {**st, "cv": cv, "mom": dml_residual_moments(pan, coef)}
 
     def phase_fit_sharded(st):
@@ -432,6 +441,8 @@ def dml_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None, G
         return {**st, "mom": dml_residual_moments(pan, st["coef"])}
 
     def phase_final(st):
+        if "res" in st:        # phase_fit's fused residual pass already wrote it
+            return st
         return {**st, "res": S.dml_finalize(st["mom"], "plr")}
 
     cap = bool(getattr(comm, "capturable", False))
@@ -643,8 +654,10 @@ def _exact_resid(pan, coef: torch.Tensor, mode: int, sh) -> torch.Tensor:
     return part
 
 
-def dml_residual_moments(pan, coef: torch.Tensor) -> torch.Tensor:
-    """Fused held-out residual pass (csrc/dml.hip) -> 7 fp64 moments."""
+def dml_residual_moments(pan, coef: torch.Tensor, final: bool = False):
+    """Fused held-out residual pass (csrc/dml.hip) -> 7 fp64 moments. ``final`` (GPU panels):
+    the same launch also sums the partials and applies the PLR formula -> (moments, res[2]),
+    the bits of this function followed by ``S.dml_finalize(mom, "plr")``."""
     K = coef.shape[0]
     p = len(pan.xcols)
     if not pan.data.is_cuda:
@@ -673,6 +686,14 @@ def dml_residual_moments(pan, coef: torch.Tensor) -> torch.Tensor:
     y0, y1 = (pan.cols["Y_hi"], pan.cols["Y_lo"]) if bf else (pan.cols["Y"], -1)
     w0, w1 = (pan.cols["W_hi"], pan.cols["W_lo"]) if bf else (pan.cols["W"], -1)
     cs, bs = pan.strides()
+    if final:
+        res = torch.empty(2, dtype=torch.float64, device=dev)
+        done = torch.zeros(1, dtype=torch.int32, device=dev)     # arrival count of the launch
+        _native.call("ate_dml_resid_moments_final", dtype_code(pan.data), pan.data.data_ptr(), cs,
+                     bs, xc.data_ptr(), p, segs.data_ptr(), K, coef.data_ptr(), y0, y1, w0, w1,
+                     pan.cols["one"], nbx, part.data_ptr(), done.data_ptr(), mom.data_ptr(),
+                     res.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return mom, res
     _native.call("ate_dml_resid_moments", dtype_code(pan.data), pan.data.data_ptr(), cs, bs,
                  xc.data_ptr(), p, segs.data_ptr(), K, coef.data_ptr(), y0, y1, w0, w1,
                  pan.cols["one"], nbx, part.data_ptr(), mom.data_ptr(),

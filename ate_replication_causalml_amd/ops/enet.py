@@ -13,6 +13,7 @@ GPU: ``csrc/enet.hip``. CPU: numpy with the same algorithm (reference core).
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -25,6 +26,15 @@ from .devconst import const, const_bytes
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+# The launches around the path kernel (csrc/enet.hip). Fused (default): one prepare launch
+# (ate_enet_prepare_fused: statistics, C with its pad columns, g, the NaN lambda table) and
+# one tail launch (ate_enet_cv_tail: coefficients, CV loss, selection, picks). ATE_CV_FUSED=0:
+# the chain of separate launches (two fills, ate_enet_prepare's two, ate_enet_coef,
+# ate_enet_cvloss_gauss, ate_cv_select, ate_enet_pick). Same bits either way
+# (profiles/call_glue). Read at import; estimators/lasso.py follows it for the residual pass.
+CV_FUSED = os.environ.get("ATE_CV_FUSED", "1") not in ("", "0")
 
 
 @dataclass
@@ -218,9 +228,26 @@ def _cv_gpu(G, P, nseg, masks, xcols, ycols, p, ny, vp, one, full_probs, fold_pr
     probs_all = list(full_probs) + list(fold_probs)
     nq = len(probs_all)
     i32 = torch.int32
-    C, apath, rsq, nlam, npass, progress = _zeroed(
-        dev, ((nt, p, ldc), torch.float32 if c_f32 else torch.float64), ((nq, L, p), torch.float64),
-        ((nq, L), torch.float64), ((nq,), i32), ((nq,), i32), ((nq,), i32))
+    c_dt = torch.float32 if c_f32 else torch.float64
+    # the selection wave holds 256 lambdas: a longer table goes down the chain of separate
+    # launches, whose ate_cv_select refuses it by name (status -1)
+    fused = CV_FUSED and L <= 256
+    # the fused prepare keeps a set's segments in registers up to 8 of them; beyond (the
+    # repeated cross-fit's S * K fold Grams) the two-launch prepare is the faster one
+    fused_prep = fused and nseg <= 8
+    if fused:
+        # the path kernel writes every apath row below nlam, the only rows the tail reads,
+        # and the fused prepare every element of C (pad columns included): not zeroed
+        zspec = [((nq, L), torch.float64), ((nq,), i32), ((nq,), i32), ((nq,), i32), ((nf,), i32)]
+        if not fused_prep:
+            zspec.append(((nt, p, ldc), c_dt))
+        rsq, nlam, npass, progress, done, *zc = _zeroed(dev, *zspec)
+        C = zc[0] if zc else torch.empty((nt, p, ldc), dtype=c_dt, device=dev)
+        apath = torch.empty((nq, L, p), **f64)
+    else:
+        C, apath, rsq, nlam, npass, progress = _zeroed(
+            dev, ((nt, p, ldc), c_dt), ((nq, L, p), torch.float64),
+            ((nq, L), torch.float64), ((nq,), i32), ((nq,), i32), ((nq,), i32))
     g = torch.empty((nt, ny, p), **f64)
     xm = torch.empty((nt, p), **f64)
     xs = torch.empty((nt, p), **f64)
@@ -228,45 +255,64 @@ def _cv_gpu(G, P, nseg, masks, xcols, ycols, p, ny, vp, one, full_probs, fold_pr
     ym = torch.empty((nt, ny), **f64)
     ys = torch.empty((nt, ny), **f64)
     nobs = torch.empty(nt, **f64)
-    _native.call("ate_enet_prepare", G.data_ptr(), nseg, P, masks_t.data_ptr(), nt, xc.data_ptr(),
-                 p, one, yc.data_ptr(), ny, C.data_ptr(), c_f32, g.data_ptr(), xm.data_ptr(),
-                 xs.data_ptr(), ju.data_ptr(), ym.data_ptr(), ys.data_ptr(), nobs.data_ptr(), s)
+    if fused_prep:
+        lams = torch.empty((nq, L), **f64)
+        _native.call("ate_enet_prepare_fused", G.data_ptr(), nseg, P, masks_t.data_ptr(), nt,
+                     xc.data_ptr(), p, one, yc.data_ptr(), ny, C.data_ptr(), c_f32, g.data_ptr(),
+                     xm.data_ptr(), xs.data_ptr(), ju.data_ptr(), ym.data_ptr(), ys.data_ptr(),
+                     nobs.data_ptr(), lams.data_ptr(), nq * L, s)
+    else:
+        _native.call("ate_enet_prepare", G.data_ptr(), nseg, P, masks_t.data_ptr(), nt,
+                     xc.data_ptr(), p, one, yc.data_ptr(), ny, C.data_ptr(), c_f32, g.data_ptr(),
+                     xm.data_ptr(), xs.data_ptr(), ju.data_ptr(), ym.data_ptr(), ys.data_ptr(),
+                     nobs.data_ptr(), s)
+        lams = torch.full((nq, L), float("nan"), **f64)
     vp_t = const(np.asarray(vp, dtype=np.float64), torch.float64, dev)
     # ONE launch: full problems [0, nf) + fold problems [nf, nq); fold problems consume
     # their source's lambda sequence as it is published (device-side progress flags)
     pr = _probs_tensor(probs_all, dev)
-    lams = torch.full((nq, L), float("nan"), **f64)
     # each full problem's whole lambda sequence, published at its lambda 1 for the folds
     lampub = torch.empty((nq, L), **f64)
     _native.call("ate_enet_path", C.data_ptr(), c_f32, g.data_ptr(), p, ny, ju.data_ptr(),
                  ys.data_ptr(), vp_t.data_ptr(), pr.data_ptr(), nq, alpha, flmin, thresh,
                  maxit, apath.data_ptr(), lams.data_ptr(), rsq.data_ptr(), nlam.data_ptr(),
                  npass.data_ptr(), L, progress.data_ptr(), lampub.data_ptr(), s)
-    coef = torch.empty((nq, L, p + 1), **f64)
-    _native.call("ate_enet_coef", apath.data_ptr(), pr.data_ptr(), nq, p, ny, L,
-                 nlam.data_ptr(), xm.data_ptr(), xs.data_ptr(), ju.data_ptr(), ym.data_ptr(),
-                 ys.data_ptr(), coef.data_ptr(), s)
     hold = const([0] * nf + list(fold_holds), torch.int32, dev)
     ycol_p = const([0] * nf + list(fold_ycol), torch.int32, dev)
     cvraw = torch.empty((nq, L), **f64)
-    _native.call("ate_enet_cvloss_gauss", G.data_ptr(), P, hold.data_ptr(), xc.data_ptr(), p, one,
-                 ycol_p.data_ptr(), coef.data_ptr(), nlam.data_ptr(), L, nf, nq - nf,
-                 cvraw.data_ptr(), s)
     fidx = const(fold_index + nf, torch.int32, dev)
     nfold_t = const(nfold, torch.float64, dev)
     cvm = torch.empty((nf, L), **f64)
     cvsd = torch.empty((nf, L), **f64)
     sel = torch.empty((nf, 2), dtype=torch.int32, device=dev)
     K = fold_index.shape[1]
+    cmin = torch.empty((nf, p + 1), **f64)
+    c1se = torch.empty((nf, p + 1), **f64)
     # a fold whose spin on its source's progress flag timed out (npass = -1; csrc/enet.hip)
     # has a truncated path: cvm, and so lambda.min / lambda.1se, would silently change --
-    # the select and pick kernels NaN-poison cvm / cvsd / the picked coefficients then
+    # the selection and the picks NaN-poison cvm / cvsd / the picked coefficients then
     fold_npass = npass[nf:]
+    if fused:
+        # the fold problems' coefficient rows live only in the tail's LDS
+        coef = torch.empty((nf, L, p + 1), **f64)
+        _native.call("ate_enet_cv_tail", G.data_ptr(), P, hold.data_ptr(), xc.data_ptr(), p, one,
+                     ycol_p.data_ptr(), apath.data_ptr(), pr.data_ptr(), ny, nlam.data_ptr(),
+                     xm.data_ptr(), xs.data_ptr(), ju.data_ptr(), ym.data_ptr(), ys.data_ptr(), L,
+                     nf, nq - nf, K, fidx.data_ptr(), nfold_t.data_ptr(), coef.data_ptr(),
+                     cvraw.data_ptr(), cvm.data_ptr(), cvsd.data_ptr(), sel.data_ptr(),
+                     cmin.data_ptr(), c1se.data_ptr(), fold_npass.data_ptr(), done.data_ptr(), s)
+        return EnetCvResult(lams[:nf], nlam[:nf], cvm, cvsd, sel, coef, cmin, c1se, full_keys,
+                            npass[:nf], fold_npass, nlam[nf:])
+    coef = torch.empty((nq, L, p + 1), **f64)
+    _native.call("ate_enet_coef", apath.data_ptr(), pr.data_ptr(), nq, p, ny, L,
+                 nlam.data_ptr(), xm.data_ptr(), xs.data_ptr(), ju.data_ptr(), ym.data_ptr(),
+                 ys.data_ptr(), coef.data_ptr(), s)
+    _native.call("ate_enet_cvloss_gauss", G.data_ptr(), P, hold.data_ptr(), xc.data_ptr(), p, one,
+                 ycol_p.data_ptr(), coef.data_ptr(), nlam.data_ptr(), L, nf, nq - nf,
+                 cvraw.data_ptr(), s)
     _native.call("ate_cv_select", cvraw.data_ptr(), fidx.data_ptr(), nfold_t.data_ptr(), K, nf,
                  nlam.data_ptr(), L, cvm.data_ptr(), cvsd.data_ptr(), sel.data_ptr(),
                  fold_npass.data_ptr(), nq - nf, s)
-    cmin = torch.empty((nf, p + 1), **f64)
-    c1se = torch.empty((nf, p + 1), **f64)
     _native.call("ate_enet_pick", coef.data_ptr(), sel.data_ptr(), p, L, nf, cmin.data_ptr(),
                  c1se.data_ptr(), fold_npass.data_ptr(), nq - nf, s)
     return EnetCvResult(lams[:nf], nlam[:nf], cvm, cvsd, sel, coef[:nf], cmin, c1se, full_keys,

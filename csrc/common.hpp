@@ -106,6 +106,17 @@ __device__ inline void block_sum(double (&v)[NV], double* smem /* >= 16*NV */) {
   __syncthreads();
 }
 
+// A result that another workgroup of the SAME launch reads after an agent-scope acquire
+// (the last-arriver tails of csrc/dml.hip and csrc/enet.hip). AGENT: the store is written
+// through to the agent's coherence point, so its writer needs no L2 write-back fence: it
+// waits for its stores (wait_stores) and then counts itself in. Plain otherwise.
+template <bool AGENT>
+__device__ __forceinline__ void st_out(double* p, double v) {
+  if constexpr (AGENT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+}
+__device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
 inline int grid_for(int64_t n, int block, int cap = 2048) {
   int64_t g = (n + block - 1) / block;
   if (g < 1) g = 1;

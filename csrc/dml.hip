@@ -9,6 +9,7 @@
 // 256 rows of a block). Coefficients for all folds are staged
 // in LDS. y/w are reconstructed from their hi+lo bf16 columns on bf16 panels.
 #include "common.hpp"
+#include "dml_common.hpp"
 
 using namespace ate;
 
@@ -53,8 +54,8 @@ __device__ int compact_support(C* cy, C* cw, int* xc, int p, int* wcnt /* [>= 4]
   return base;
 }
 
-template <typename T, int RPT>
-__global__ __launch_bounds__(256) void dml_resid_kernel(
+template <typename T, int RPT, bool AGENT = false>
+__device__ __forceinline__ void dml_resid_body(
     const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p,
     const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef /*[nseg][2][p+1]*/,
     int y0, int y1, int w0, int w1, int vcol, double* __restrict__ partial) {
@@ -112,20 +113,26 @@ __global__ __launch_bounds__(256) void dml_resid_kernel(
   if (threadIdx.x == 0) {
     double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 7;
 #pragma unroll
-    for (int q = 0; q < 7; ++q) out[q] = v[q];
+    for (int q = 0; q < 7; ++q) st_out<AGENT>(out + q, v[q]);
   }
 }
 
+template <typename T, int RPT>
+__global__ __launch_bounds__(256) void dml_resid_kernel(
+    const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p,
+    const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef /*[nseg][2][p+1]*/,
+    int y0, int y1, int w0, int w1, int vcol, double* __restrict__ partial) {
+  dml_resid_body<T, RPT>(X, ld, xcols, p, segs, nseg, coef, y0, y1, w0, w1, vcol, partial);
+}
+
 // one block of 256 threads: thread i sums partials i, i+256, ... (fixed order), then a
-// fixed-shape block reduction -> deterministic for a given launch geometry
+// fixed-shape block reduction -> deterministic for a given launch geometry (sum7_block,
+// csrc/dml_common.hpp)
 __global__ __launch_bounds__(256) void sum7_kernel(const double* __restrict__ partial, int nb,
                                                    double* __restrict__ out) {
   __shared__ double red[16 * 7];
   double v[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int b = threadIdx.x; b < nb; b += 256)
-#pragma unroll
-    for (int q = 0; q < 7; ++q) v[q] += partial[(int64_t)b * 7 + q];
-  block_sum<7>(v, red);
+  sum7_block(partial, nb, v, red);
   if (threadIdx.x == 0)
 #pragma unroll
     for (int q = 0; q < 7; ++q) out[q] = v[q];
@@ -155,7 +162,8 @@ static int dml_resid_t(const void* X, int64_t ld, const void* xcols, int p, cons
 // 2 = per-term int64 limb sums at the shifts sh[7] derived from the global max
 // (partial [blocks][14] int64: hi limbs, then lo limbs) -- integer sums, so the block and
 // the rank that own a row cannot change the result.
-__global__ __launch_bounds__(256) void dml_resid_bf16_kernel(
+template <bool AGENT = false>
+__device__ __forceinline__ void dml_resid_bf16_body(
     const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
     const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef,
     int y0, int y1, int w0, int w1, int vcol, double* __restrict__ partial, int mode,
@@ -244,7 +252,7 @@ __global__ __launch_bounds__(256) void dml_resid_bf16_kernel(
     if (threadIdx.x == 0) {
       double* out = partial + blk * 7;
 #pragma unroll
-      for (int q = 0; q < 7; ++q) out[q] = v[q];
+      for (int q = 0; q < 7; ++q) st_out<AGENT>(out + q, v[q]);
     }
     return;
   }
@@ -285,6 +293,99 @@ __global__ __launch_bounds__(256) void dml_resid_bf16_kernel(
       reinterpret_cast<long long*>(partial)[blk * 14 + q] = a;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void dml_resid_bf16_kernel(
+    const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
+    const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef,
+    int y0, int y1, int w0, int w1, int vcol, double* __restrict__ partial, int mode,
+    const int64_t* __restrict__ sh) {
+  dml_resid_bf16_body(X, cs, bs, xcols, p, segs, nseg, coef, y0, y1, w0, w1, vcol, partial, mode,
+                      sh);
+}
+
+// ------------------------------------------------------------------ residual pass + its own tail
+// The residual kernels above, then the workgroup that arrives last does sum7_kernel's sum
+// and dml_finalize_kernel's PLR formula (csrc/dml_common.hpp: the same expressions, so the
+// same bits as ate_dml_resid_moments + ate_dml_finalize(mode 0)). Thread 0 of every workgroup
+// has written its partial through to the agent's coherence point (st_out<true>), waits for
+// those stores and then counts the workgroup in *done, which the caller hands in zeroed;
+// nobody waits. (A fence in every wave instead cost 0.3 ms per call: each one writes the L2
+// back and invalidates it under the streaming reads.) Whole block must call it.
+__device__ __forceinline__ void dml_resid_final_tail(const double* partial, int* done,
+                                                     double* __restrict__ mom,
+                                                     double* __restrict__ res) {
+  __shared__ double red[16 * 7];
+  __shared__ int slast;
+  const int nb = gridDim.x * gridDim.y;
+  if (threadIdx.x == 0) {
+    wait_stores();
+    const int old = __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ATE_DASSERT(old >= 0 && old < nb);
+    slast = old == nb - 1;
+  }
+  __syncthreads();
+  if (!slast) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  double v[7] = {0, 0, 0, 0, 0, 0, 0};
+  sum7_block(partial, nb, v, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < 7; ++q) mom[q] = v[q];
+    dml_finalize_formula(v, 0, res);
+  }
+}
+
+template <typename T, int RPT>
+__global__ __launch_bounds__(256) void dml_resid_final_kernel(
+    const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p,
+    const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef, int y0, int y1,
+    int w0, int w1, int vcol, double* partial, int* done, double* __restrict__ mom,
+    double* __restrict__ res) {
+  dml_resid_body<T, RPT, true>(X, ld, xcols, p, segs, nseg, coef, y0, y1, w0, w1, vcol, partial);
+  dml_resid_final_tail(partial, done, mom, res);
+}
+
+__global__ __launch_bounds__(256) void dml_resid_bf16_final_kernel(
+    const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
+    const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef, int y0, int y1,
+    int w0, int w1, int vcol, double* partial, int* done, double* __restrict__ mom,
+    double* __restrict__ res) {
+  dml_resid_bf16_body<true>(X, cs, bs, xcols, p, segs, nseg, coef, y0, y1, w0, w1, vcol, partial,
+                            0, nullptr);
+  dml_resid_final_tail(partial, done, mom, res);
+}
+
+// ate_dml_resid_moments and ate_dml_finalize (PLR) in ONE launch: moments[7] and res[2].
+// done: one int32, zero at launch (left at nseg*nbx).
+ATE_API int ate_dml_resid_moments_final(int dtype, const void* X, int64_t cs, int64_t bs,
+                                        const void* xcols, int p, const void* segs, int nseg,
+                                        const void* coef, int y0, int y1, int w0, int w1,
+                                        int vcol, int nbx, void* partial, void* done,
+                                        void* moments, void* res, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype != 3 && bs != 64) return -1;
+  if (nbx < 1 || nseg < 1) return -1;
+  dim3 grid(nbx, nseg);
+  const size_t shd = (size_t)2 * (p + 1) * sizeof(double) + (size_t)p * sizeof(int);
+  if (dtype == 1) {
+    ATE_LAUNCH((dml_resid_final_kernel<float, 4>), grid, dim3(256), shd, s, (const float*)X, cs,
+               (const int*)xcols, p, (const Seg*)segs, nseg, (const double*)coef, y0, y1, w0, w1,
+               vcol, (double*)partial, (int*)done, (double*)moments, (double*)res);
+  } else if (dtype == 2) {
+    ATE_LAUNCH((dml_resid_final_kernel<double, 4>), grid, dim3(256), shd, s, (const double*)X, cs,
+               (const int*)xcols, p, (const Seg*)segs, nseg, (const double*)coef, y0, y1, w0, w1,
+               vcol, (double*)partial, (int*)done, (double*)moments, (double*)res);
+  } else if (dtype == 3) {
+    const size_t sh = (size_t)2 * (p + 1) * sizeof(float) + (size_t)p * sizeof(int);
+    ATE_LAUNCH(dml_resid_bf16_final_kernel, grid, dim3(256), sh, s, (const bf16_t*)X, cs, bs,
+               (const int*)xcols, p, (const Seg*)segs, nseg, (const double*)coef, y0, y1, w0, w1,
+               vcol, (double*)partial, (int*)done, (double*)moments, (double*)res);
+  } else {
+    return -1;
+  }
+  ATE_CHECK_LAUNCH();
+  return 0;
 }
 
 // dtype 1 f32, 2 f64, 3 bf16. partial: [nseg*nbx*7]

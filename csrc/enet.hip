@@ -41,6 +41,18 @@ __device__ __forceinline__ double seg_sum(const double* __restrict__ G, int nseg
   return acc;
 }
 
+// glmnet `standard` expressions, shared by the two-launch chain and the fused launch (one
+// definition: the same contraction, so the same bits)
+__device__ __forceinline__ void col_mean_var(double s1, double s2, double n, double& m,
+                                             double& v) {
+  m = s1 / n;
+  v = s2 / n - m * m;
+}
+__device__ __forceinline__ double std_entry(double sab, double n, double ma, double mb,
+                                            double sa, double sb) {
+  return (sab / n - ma * mb) / (sa * sb);
+}
+
 __global__ __launch_bounds__(256) void enet_prep_stats_kernel(
     const double* __restrict__ G, int nseg, int P, const unsigned char* __restrict__ masks,
     const int* __restrict__ xcols, int p, int ones_col, const int* __restrict__ ycols, int ny,
@@ -52,16 +64,18 @@ __global__ __launch_bounds__(256) void enet_prep_stats_kernel(
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < p) {
     const int j = e;
-    const double mj = seg_sum(G, nseg, P, mk, ones_col, xcols[j]) / n;
-    const double vj = seg_sum(G, nseg, P, mk, xcols[j], xcols[j]) / n - mj * mj;
+    double mj, vj;
+    col_mean_var(seg_sum(G, nseg, P, mk, ones_col, xcols[j]),
+                 seg_sum(G, nseg, P, mk, xcols[j], xcols[j]), n, mj, vj);
     xm[(int64_t)s * p + j] = mj;
     xs[(int64_t)s * p + j] = vj > 0 ? sqrt(vj) : 1.0;
     ju[(int64_t)s * p + j] = vj > 0 ? 1 : 0;
     if (j == 0) nobs[s] = n;
   } else if (e < p + ny) {
     const int y = e - p;
-    const double my = seg_sum(G, nseg, P, mk, ones_col, ycols[y]) / n;
-    const double vy = seg_sum(G, nseg, P, mk, ycols[y], ycols[y]) / n - my * my;
+    double my, vy;
+    col_mean_var(seg_sum(G, nseg, P, mk, ones_col, ycols[y]),
+                 seg_sum(G, nseg, P, mk, ycols[y], ycols[y]), n, my, vy);
     ym[(int64_t)s * ny + y] = my;
     ys[(int64_t)s * ny + y] = vy > 0 ? sqrt(vy) : 1.0;
   }
@@ -92,8 +106,8 @@ __global__ __launch_bounds__(256) void enet_prepare_kernel(
         cjk = (j == k) ? 1.0 : 0.0;
       } else {
         const double mj = xm[(int64_t)s * p + j], mk2 = xm[(int64_t)s * p + k];
-        cjk = (seg_sum(G, nseg, P, mk, xcols[j], xcols[k]) / n - mj * mk2) /
-              (xs[(int64_t)s * p + j] * xs[(int64_t)s * p + k]);
+        cjk = std_entry(seg_sum(G, nseg, P, mk, xcols[j], xcols[k]), n, mj, mk2,
+                        xs[(int64_t)s * p + j], xs[(int64_t)s * p + k]);
       }
       C[((int64_t)s * p + j) * ldc + k] = (CT)cjk;
     } else {
@@ -102,8 +116,8 @@ __global__ __launch_bounds__(256) void enet_prepare_kernel(
       double gj = 0.0;
       if (ju[(int64_t)s * p + j]) {
         const double mj = xm[(int64_t)s * p + j], my = ym[(int64_t)s * ny + y];
-        gj = (seg_sum(G, nseg, P, mk, xcols[j], ycols[y]) / n - mj * my) /
-             (xs[(int64_t)s * p + j] * ys[(int64_t)s * ny + y]);
+        gj = std_entry(seg_sum(G, nseg, P, mk, xcols[j], ycols[y]), n, mj, my,
+                       xs[(int64_t)s * p + j], ys[(int64_t)s * ny + y]);
       }
       g[((int64_t)s * ny + y) * p + j] = gj;
     }
@@ -135,6 +149,194 @@ ATE_API int ate_enet_prepare(const void* G, int nseg, int P, const void* masks, 
                        (const int*)ycols, ny, (const double*)xm, (const double*)xs,
                        (const unsigned char*)ju, (const double*)ym, (const double*)ys,
                        (const double*)nobs, (double*)C, (double*)g);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ prepare, one launch
+// The same outputs as ate_enet_prepare (same bits: col_mean_var / std_entry / seg_sum's
+// order), plus what the caller otherwise fills: C's pad columns [p, ldc) = 0 and lams = NaN.
+// Workgroup (tk, tj, tz) owns the PF_TJ x PF_TK tile j in [16 tj, +16), k in [64 tk, +64) of
+// the p x ldc matrix for the PF_SCH training sets [4 tz, +4): a thread loads the nseg Gram
+// entries of its 4 elements once and forms each set's masked sum from registers, in segment
+// order (nseg <= PF_SEG; above that it reads them per set, as seg_sum does). Every masked
+// sum loads all its segments first and adds the set's in order: the loads overlap instead
+// of waiting one L2 round trip per segment behind the mask branch. Each workgroup recomputes
+// the column statistics of its 16 + 64 columns for its sets in LDS; the workgroups of the
+// first tile column (tk = 0) also write xm / xs / ju and g for their j range, workgroups
+// (0, 0, tz) also ym / ys / nobs. (j, k) and (k, j) each read their own Gram entry: G need
+// not be symmetric. (All sets in one workgroup -- 256 workgroups at p = 500, one wave per
+// SIMD under 60 serial fp64 divisions a thread -- took 71 us; see profiles/call_glue.)
+constexpr int PF_TJ = 16, PF_TK = 64, PF_NC = PF_TJ + PF_TK, PF_SCH = 4, PF_SEG = 8;
+
+// seg_sum with the set's mask as bits (nseg <= PF_SEG): the same additions in the same order
+__device__ __forceinline__ double seg_sum_bits(const double* __restrict__ G, int nseg, int P,
+                                               unsigned bits, int a, int b) {
+  double v[PF_SEG];
+#pragma unroll
+  for (int q = 0; q < PF_SEG; ++q) v[q] = q < nseg ? G[((int64_t)q * P + a) * P + b] : 0.0;
+  double acc = 0.0;
+#pragma unroll
+  for (int q = 0; q < PF_SEG; ++q)
+    if (q < nseg && (bits >> q & 1u)) acc += v[q];
+  return acc;
+}
+
+template <typename CT>
+__global__ __launch_bounds__(256) void enet_prepare_fused_kernel(
+    const double* __restrict__ G, int nseg, int P, const unsigned char* __restrict__ masks,
+    int ntrain, const int* __restrict__ xcols, int p, int ldc, int ones_col,
+    const int* __restrict__ ycols, int ny, CT* __restrict__ C, double* __restrict__ g,
+    double* __restrict__ xm, double* __restrict__ xs, unsigned char* __restrict__ ju,
+    double* __restrict__ ym, double* __restrict__ ys, double* __restrict__ nobs,
+    double* __restrict__ lams, int64_t nlams) {
+  const int tk = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  const int j0 = tj * PF_TJ, k0 = tk * PF_TK, s0 = blockIdx.z * PF_SCH;
+  const int lane = tid & 63, jr = tid >> 6;
+  ATE_DASSERT(k0 + PF_TK <= ldc && j0 < p && ones_col >= 0 && ones_col < P);
+  {
+    const int64_t nb = (int64_t)gridDim.x * gridDim.y * gridDim.z,
+                  b = ((int64_t)blockIdx.z * gridDim.y + tj) * gridDim.x + tk;
+    for (int64_t e = b * 256 + tid; e < nlams; e += nb * 256) lams[e] = __builtin_nan("");
+  }
+  __shared__ double s_n[PF_SCH], s_m[PF_SCH][PF_NC], s_s[PF_SCH][PF_NC];
+  __shared__ unsigned char s_ju[PF_SCH][PF_NC];
+  __shared__ unsigned s_mask[PF_SCH];
+  const bool inreg = nseg <= PF_SEG;
+  const int k = k0 + lane;
+  const int xk = k < p ? xcols[k] : 0;
+  ATE_DASSERT(xk >= 0 && xk < P);
+  // this thread's elements (j0 + jr + 4 i, k): their nseg Gram entries, loaded once
+  double gv[4][PF_SEG];
+  int xj[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int j = j0 + jr + 4 * i;
+    xj[i] = j < p ? xcols[j] : 0;
+    ATE_DASSERT(xj[i] >= 0 && xj[i] < P);
+#pragma unroll
+    for (int q = 0; q < PF_SEG; ++q)
+      gv[i][q] = (inreg && q < nseg && j < p && k < p)
+                     ? G[((int64_t)q * P + xj[i]) * P + xk] : 0.0;
+  }
+  // a set's masked sum of entry (a, b)
+  auto set_sum = [&](int s, int sl, int a, int b) {
+    return inreg ? seg_sum_bits(G, nseg, P, s_mask[sl], a, b)
+                 : seg_sum(G, nseg, P, masks + (int64_t)s * nseg, a, b);
+  };
+  {
+    const int ns = ntrain - s0 < PF_SCH ? ntrain - s0 : PF_SCH;
+    ATE_DASSERT(ns >= 1);
+    if (tid < ns) {
+      const unsigned char* mk = masks + (int64_t)(s0 + tid) * nseg;
+      unsigned bits = 0;
+      if (inreg) {
+#pragma unroll
+        for (int q = 0; q < PF_SEG; ++q) bits |= (q < nseg && mk[q < nseg ? q : 0]) ? 1u << q : 0u;
+      }
+      s_mask[tid] = bits;
+      s_n[tid] = inreg ? seg_sum_bits(G, nseg, P, bits, ones_col, ones_col)
+                       : seg_sum(G, nseg, P, mk, ones_col, ones_col);
+    }
+    __syncthreads();
+    for (int e = tid; e < ns * PF_NC; e += 256) {
+      const int sl = e / PF_NC, c = e % PF_NC;
+      const int col = c < PF_TJ ? j0 + c : k0 + c - PF_TJ;
+      if (col >= p) continue;
+      const int s = s0 + sl;
+      const int xc = xcols[col];
+      ATE_DASSERT(xc >= 0 && xc < P);
+      double mj, vj;
+      col_mean_var(set_sum(s, sl, ones_col, xc), set_sum(s, sl, xc, xc), s_n[sl], mj, vj);
+      const double sd = vj > 0 ? sqrt(vj) : 1.0;
+      s_m[sl][c] = mj;
+      s_s[sl][c] = sd;
+      s_ju[sl][c] = vj > 0 ? 1 : 0;
+      if (tk == 0 && c < PF_TJ) {
+        xm[(int64_t)s * p + col] = mj;
+        xs[(int64_t)s * p + col] = sd;
+        ju[(int64_t)s * p + col] = vj > 0 ? 1 : 0;
+      }
+    }
+    if (tk == 0 && tj == 0) {
+      if (tid < ns) nobs[s0 + tid] = s_n[tid];
+      for (int e = tid; e < ns * ny; e += 256) {
+        const int sl = e / ny, y = e % ny, s = s0 + sl;
+        double my, vy;
+        col_mean_var(set_sum(s, sl, ones_col, ycols[y]), set_sum(s, sl, ycols[y], ycols[y]),
+                     s_n[sl], my, vy);
+        ym[(int64_t)s * ny + y] = my;
+        ys[(int64_t)s * ny + y] = vy > 0 ? sqrt(vy) : 1.0;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int jl = jr + 4 * i, j = j0 + jl;
+      if (j >= p) continue;
+      for (int sl = 0; sl < ns; ++sl) {
+        const int s = s0 + sl;
+        double cjk = 0.0;                  // the pad columns [p, ldc)
+        if (k < p) {
+          if (!s_ju[sl][jl] || !s_ju[sl][PF_TJ + lane]) {
+            cjk = (j == k) ? 1.0 : 0.0;
+          } else {
+            double acc = 0.0;
+            if (inreg) {
+              const unsigned bits = s_mask[sl];
+#pragma unroll
+              for (int q = 0; q < PF_SEG; ++q)
+                if (q < nseg && (bits >> q & 1u)) acc += gv[i][q];
+            } else {
+              acc = seg_sum(G, nseg, P, masks + (int64_t)s * nseg, xj[i], xk);
+            }
+            cjk = std_entry(acc, s_n[sl], s_m[sl][jl], s_m[sl][PF_TJ + lane], s_s[sl][jl],
+                            s_s[sl][PF_TJ + lane]);
+          }
+        }
+        C[((int64_t)s * p + j) * ldc + k] = (CT)cjk;
+      }
+    }
+    if (tk == 0) {
+      for (int e = tid; e < ns * ny * PF_TJ; e += 256) {
+        const int jl = e % PF_TJ, y = (e / PF_TJ) % ny, sl = e / (PF_TJ * ny);
+        const int j = j0 + jl, s = s0 + sl;
+        if (j >= p) continue;
+        double gj = 0.0;
+        if (s_ju[sl][jl]) {
+          const int yc = ycols[y];
+          ATE_DASSERT(yc >= 0 && yc < P);
+          double my, vy;
+          col_mean_var(set_sum(s, sl, ones_col, yc), set_sum(s, sl, yc, yc), s_n[sl], my, vy);
+          gj = std_entry(set_sum(s, sl, xcols[j], yc), s_n[sl], s_m[sl][jl], my, s_s[sl][jl],
+                         vy > 0 ? sqrt(vy) : 1.0);
+        }
+        g[((int64_t)s * ny + y) * p + j] = gj;
+      }
+    }
+  }
+}
+
+// lams: nlams doubles set to NaN (the path launch's lambda table); C need not be zeroed.
+ATE_API int ate_enet_prepare_fused(const void* G, int nseg, int P, const void* masks, int ntrain,
+                                   const void* xcols, int p, int ones_col, const void* ycols,
+                                   int ny, void* C, int c_f32, void* g, void* xm, void* xs,
+                                   void* ju, void* ym, void* ys, void* nobs, void* lams,
+                                   int64_t nlams, void* stream) {
+  if (p < 1 || ntrain < 1 || nseg < 1 || ny < 0) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const int ldc = (p + 63) / 64 * 64;   // padded row stride
+  dim3 grid(ldc / PF_TK, (p + PF_TJ - 1) / PF_TJ, (ntrain + PF_SCH - 1) / PF_SCH);
+  if (c_f32)
+    ATE_LAUNCH(enet_prepare_fused_kernel<float>, grid, dim3(256), 0, st, (const double*)G, nseg,
+               P, (const unsigned char*)masks, ntrain, (const int*)xcols, p, ldc, ones_col,
+               (const int*)ycols, ny, (float*)C, (double*)g, (double*)xm, (double*)xs,
+               (unsigned char*)ju, (double*)ym, (double*)ys, (double*)nobs, (double*)lams, nlams);
+  else
+    ATE_LAUNCH(enet_prepare_fused_kernel<double>, grid, dim3(256), 0, st, (const double*)G, nseg,
+               P, (const unsigned char*)masks, ntrain, (const int*)xcols, p, ldc, ones_col,
+               (const int*)ycols, ny, (double*)C, (double*)g, (double*)xm, (double*)xs,
+               (unsigned char*)ju, (double*)ym, (double*)ys, (double*)nobs, (double*)lams, nlams);
   ATE_CHECK_LAUNCH();
   return 0;
 }
@@ -1647,6 +1849,25 @@ ATE_API int ate_enet_path(const void* C, int c_f32, const void* g, int p, int ny
 
 // ------------------------------------------------------------------ coefficients (original scale)
 // coef[q][m][0] = intercept, coef[q][m][1+j] = beta_j = a_j * ys / xs_j (0 if !ju)
+// One thread's share (j = t0, t0 + stride, ...) of a coefficient row: st(j, beta_j) for each,
+// and its part of sum beta_j xm_j (the intercept is ym minus the sum over the row's threads).
+// tb = train * p. Shared by enet_coef_kernel and enet_cv_tail_kernel.
+template <class Store>
+__device__ __forceinline__ double coef_row_terms(const double* __restrict__ a, int64_t tb, int p,
+                                                 double ysq, const double* __restrict__ xm,
+                                                 const double* __restrict__ xs,
+                                                 const unsigned char* __restrict__ ju, int t0,
+                                                 int stride, Store st) {
+  double acc = 0.0;
+  for (int j = t0; j < p; j += stride) {
+    int64_t sj = tb + j;
+    double b = ju[sj] ? a[j] * ysq / xs[sj] : 0.0;
+    st(j, b);
+    acc += b * xm[sj];
+  }
+  return acc;
+}
+
 __global__ void enet_coef_kernel(const double* __restrict__ apath, const EnetProblem* __restrict__ probs,
                                  int nprob, int p, int ny, int L, const int* __restrict__ nlam_out,
                                  const double* __restrict__ xm, const double* __restrict__ xs,
@@ -1663,13 +1884,8 @@ __global__ void enet_coef_kernel(const double* __restrict__ apath, const EnetPro
   const double* a = apath + ((int64_t)q * L + m) * p;
   const double ysq = ys[(int64_t)pr.train * ny + pr.y], ymq = ym[(int64_t)pr.train * ny + pr.y];
   __shared__ double smem[16];
-  double acc[1] = {0.0};
-  for (int j = threadIdx.x; j < p; j += blockDim.x) {
-    int64_t sj = (int64_t)pr.train * p + j;
-    double b = ju[sj] ? a[j] * ysq / xs[sj] : 0.0;
-    out[1 + j] = b;
-    acc[0] += b * xm[sj];
-  }
+  double acc[1] = {coef_row_terms(a, (int64_t)pr.train * p, p, ysq, xm, xs, ju, threadIdx.x,
+                                  blockDim.x, [&](int j, double b) { out[1 + j] = b; })};
   block_sum<1>(acc, smem);
   if (threadIdx.x == 0) out[0] = ymq - acc[0];
 }
@@ -1701,32 +1917,16 @@ ATE_API int ate_enet_coef(const void* apath, const void* probs, int nprob, int p
 constexpr int CVL = 8;
 constexpr int CVK = PMAX / 64;
 
-__global__ __launch_bounds__(256) void enet_cvloss_gauss_kernel(
-    const double* __restrict__ G, int P, const int* __restrict__ hold,
-    const int* __restrict__ xcols, int p, int ones_col, const int* __restrict__ ycol_of_prob,
-    const double* __restrict__ coef, const int* __restrict__ nlam_out, int L, int q0,
-    double* __restrict__ cvraw) {
-  // grid (problem, chunk), chunks dispatched densest first: the last lambdas (largest
-  // supports) start in the first round, so the workgroups past one round of the chip are
-  // the sparse early-lambda chunks that skip most rows
-  const int q = q0 + blockIdx.x, m0 = (gridDim.y - 1 - blockIdx.y) * CVL;
-  const int nl = nlam_out[q];
+// One chunk's loss from its CVL coefficient rows staged in sbeta (dense, zeros off the support
+// and beyond p / nl; written by the caller, not yet synchronised): cvq[m0 + m] for m < CVL.
+// a0_of(m): row m's intercept (read after a barrier). Whole 256-thread block must call it.
+// AGENT: the losses are read by another workgroup of this launch (st_out, csrc/common.hpp).
+template <bool AGENT, class A0>
+__device__ __forceinline__ void cvloss_chunk(
+    const double* __restrict__ Gh, int P, const int* __restrict__ xcols, int p, int ones_col,
+    int yc, double (*sbeta)[PMAX], int* sxc, unsigned char* snz, double (*sred)[3 * CVL], int nl,
+    int m0, int L, double* __restrict__ cvq, A0 a0_of) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (m0 >= nl) {
-    if (tid < CVL && m0 + tid < L) cvraw[(int64_t)q * L + m0 + tid] = NAN;
-    return;
-  }
-  const double* Gh = G + (int64_t)hold[q] * P * P;
-  const int yc = ycol_of_prob[q];
-  __shared__ double sbeta[CVL][PMAX];
-  __shared__ int sxc[PMAX];
-  __shared__ unsigned char snz[PMAX];
-  __shared__ double sred[4][3 * CVL];
-  for (int e = tid; e < CVL * PMAX; e += 256) {
-    const int m = e / PMAX, j = e % PMAX;
-    const bool ok = j < p && m0 + m < nl;
-    sbeta[m][j] = ok ? coef[((int64_t)q * L + m0 + m) * (p + 1) + 1 + j] : 0.0;
-  }
   for (int j = tid; j < PMAX; j += 256) sxc[j] = j < p ? xcols[j] : xcols[0];
   __syncthreads();
   for (int j = tid; j < PMAX; j += 256) {
@@ -1806,17 +2006,48 @@ __global__ __launch_bounds__(256) void enet_cvloss_gauss_kernel(
   if (tid < CVL && m0 + tid < L) {
     const int m = tid;
     if (m0 + m >= nl) {
-      cvraw[(int64_t)q * L + m0 + m] = NAN;
+      st_out<AGENT>(cvq + m0 + m, NAN);
     } else {
       const double qd = sred[0][m] + sred[1][m] + sred[2][m] + sred[3][m];
       const double ln = sred[0][CVL + m], s1 = sred[0][2 * CVL + m];
-      const double a0 = coef[((int64_t)q * L + m0 + m) * (p + 1)];
+      const double a0 = a0_of(m);
       const double n = Gh[(int64_t)ones_col * P + ones_col];
       const double yy = Gh[(int64_t)yc * P + yc], sy = Gh[(int64_t)ones_col * P + yc];
       const double sse = yy - 2.0 * a0 * sy - 2.0 * ln + n * a0 * a0 + 2.0 * a0 * s1 + qd;
-      cvraw[(int64_t)q * L + m0 + m] = sse / n;
+      st_out<AGENT>(cvq + m0 + m, sse / n);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void enet_cvloss_gauss_kernel(
+    const double* __restrict__ G, int P, const int* __restrict__ hold,
+    const int* __restrict__ xcols, int p, int ones_col, const int* __restrict__ ycol_of_prob,
+    const double* __restrict__ coef, const int* __restrict__ nlam_out, int L, int q0,
+    double* __restrict__ cvraw) {
+  // grid (problem, chunk), chunks dispatched densest first: the last lambdas (largest
+  // supports) start in the first round, so the workgroups past one round of the chip are
+  // the sparse early-lambda chunks that skip most rows
+  const int q = q0 + blockIdx.x, m0 = (gridDim.y - 1 - blockIdx.y) * CVL;
+  const int nl = nlam_out[q];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (m0 >= nl) {
+    if (tid < CVL && m0 + tid < L) cvraw[(int64_t)q * L + m0 + tid] = NAN;
+    return;
+  }
+  const double* Gh = G + (int64_t)hold[q] * P * P;
+  const int yc = ycol_of_prob[q];
+  __shared__ double sbeta[CVL][PMAX];
+  __shared__ int sxc[PMAX];
+  __shared__ unsigned char snz[PMAX];
+  __shared__ double sred[4][3 * CVL];
+  for (int e = tid; e < CVL * PMAX; e += 256) {
+    const int m = e / PMAX, j = e % PMAX;
+    const bool ok = j < p && m0 + m < nl;
+    sbeta[m][j] = ok ? coef[((int64_t)q * L + m0 + m) * (p + 1) + 1 + j] : 0.0;
+  }
+  cvloss_chunk<false>(Gh, P, xcols, p, ones_col, yc, sbeta, sxc, snz, sred, nl, m0, L,
+                      cvraw + (int64_t)q * L,
+                      [&](int m) { return coef[((int64_t)q * L + m0 + m) * (p + 1)]; });
 }
 
 // q0: first problem to score (problems before it -- the full-data fits -- have no
@@ -1852,15 +2083,17 @@ __device__ __forceinline__ bool any_truncated(const int* fnp, int nfp) {
   return __syncthreads_or(bad) != 0;
 }
 
-__global__ __launch_bounds__(64) void cv_select_kernel(
+// The selection of full problem f by ONE full wave (lane = 0..63); bad: any_truncated of the
+// launch. Shared by cv_select_kernel and enet_cv_tail_kernel. The picked indices also come
+// back in every lane (i_min, i_1se).
+__device__ __forceinline__ void cv_select_wave(
     const double* __restrict__ cvraw, const int* __restrict__ fold_probs,
-    const double* __restrict__ nfold, int K, int nfull, const int* __restrict__ nlam_full, int L,
-    double* __restrict__ cvm, double* __restrict__ cvsd, int* __restrict__ sel,
-    const int* __restrict__ fnp, int nfp) {
-  const int f = blockIdx.x;
-  const int lane = threadIdx.x;
-  if (f >= nfull) return;
-  if (any_truncated(fnp, nfp)) {
+    const double* __restrict__ nfold, int K, int f, const int* __restrict__ nlam_full, int L,
+    double* __restrict__ cvm, double* __restrict__ cvsd, int* __restrict__ sel, bool bad,
+    int lane, int& i_min, int& i_1se) {
+  i_min = 0;
+  i_1se = 0;
+  if (bad) {
     for (int m = lane; m < L; m += 64) {
       cvm[(int64_t)f * L + m] = NAN;
       cvsd[(int64_t)f * L + m] = NAN;
@@ -1927,6 +2160,21 @@ __global__ __launch_bounds__(64) void cv_select_kernel(
     sel[2 * f] = imin;
     sel[2 * f + 1] = i1;
   }
+  i_min = imin;
+  i_1se = i1;
+}
+
+__global__ __launch_bounds__(64) void cv_select_kernel(
+    const double* __restrict__ cvraw, const int* __restrict__ fold_probs,
+    const double* __restrict__ nfold, int K, int nfull, const int* __restrict__ nlam_full, int L,
+    double* __restrict__ cvm, double* __restrict__ cvsd, int* __restrict__ sel,
+    const int* __restrict__ fnp, int nfp) {
+  const int f = blockIdx.x;
+  const int lane = threadIdx.x;
+  if (f >= nfull) return;
+  int i0, i1;
+  cv_select_wave(cvraw, fold_probs, nfold, K, f, nlam_full, L, cvm, cvsd, sel,
+                 any_truncated(fnp, nfp), lane, i0, i1);
 }
 
 ATE_API int ate_cv_select(const void* cvraw, const void* fold_probs, const void* nfold, int K,
@@ -1962,6 +2210,157 @@ ATE_API int ate_enet_pick(const void* coef, const void* sel, int p, int L, int n
   ATE_LAUNCH(enet_pick_kernel, dim3(nfull, 2), dim3(128), 0, (hipStream_t)stream,
                      (const double*)coef, (const int*)sel, p, L, nfull, (double*)out_min,
                      (double*)out_1se, (const int*)fold_npass, nfp);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ CV tail, one launch
+// ate_enet_coef + ate_enet_cvloss_gauss + ate_cv_select + ate_enet_pick in ONE grid, same
+// bits (coef_row_terms / cvloss_chunk / cv_select_wave are the chain's own code):
+//  * workgroups [0, nfp * nch): CV-loss chunks, densest first as in enet_cvloss_gauss_kernel.
+//    A chunk builds its <= CVL coefficient rows in LDS straight from apath (two rows at a
+//    time, 128 threads each: enet_coef_kernel's strided sum and two-wave block_sum shape),
+//    so the fold problems' coefficients never touch HBM;
+//  * workgroups [nfp * nch, + nf * L): coefficient rows of the full problems (coef[:nf]);
+//  * every workgroup of full problem f (its L rows, and the nch chunks of each of its K fold
+//    problems) writes what the selection reads (coef[:nf], cvraw) through to the agent's
+//    coherence point (st_out<true>), waits for those stores and counts itself in done[f]
+//    (zero at launch). Whoever counts L + K nch takes an acquire fence and runs the
+//    selection and the two picks of f. Nobody waits. (A fence in every wave instead
+//    doubled the kernel's time: each one writes the L2 back and invalidates it under the
+//    other workgroups' Gram reads.)
+__global__ __launch_bounds__(256) void enet_cv_tail_kernel(
+    const double* __restrict__ G, int P, const int* __restrict__ hold,
+    const int* __restrict__ xcols, int p, int ones_col, const int* __restrict__ ycol_of_prob,
+    const double* __restrict__ apath, const EnetProblem* __restrict__ probs, int ny,
+    const int* __restrict__ nlam_out, const double* __restrict__ xm,
+    const double* __restrict__ xs, const unsigned char* __restrict__ ju,
+    const double* __restrict__ ym, const double* __restrict__ ys, int L, int nf, int nfp, int K,
+    const int* __restrict__ fold_probs, const double* __restrict__ nfold, double* coef,
+    double* cvraw, double* cvm, double* cvsd, int* sel, double* out_min, double* out_1se,
+    const int* __restrict__ fnp, int* done) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nch = (L + CVL - 1) / CVL, ncv = nfp * nch;
+  const int b = blockIdx.x;
+  __shared__ double sbeta[CVL][PMAX];
+  __shared__ int sxc[PMAX];
+  __shared__ unsigned char snz[PMAX];
+  __shared__ double sred[4][3 * CVL];
+  __shared__ double sw[CVL][2], sa0[CVL];
+  __shared__ int slast, ssel[2];
+  int f;
+  if (b < ncv) {
+    const int q = nf + b % nfp, m0 = (nch - 1 - b / nfp) * CVL;
+    const EnetProblem pr = probs[q];
+    f = pr.ulam_src;
+    ATE_DASSERT(f >= 0 && f < nf && pr.train >= 0 && pr.y >= 0 && pr.y < ny);
+    const int nl = nlam_out[q];
+    if (m0 >= nl) {
+      if (tid < CVL && m0 + tid < L) st_out<true>(cvraw + (int64_t)q * L + m0 + tid, NAN);
+    } else {
+      const double* Gh = G + (int64_t)hold[q] * P * P;
+      const int yc = ycol_of_prob[q];
+      const double ysq = ys[(int64_t)pr.train * ny + pr.y], ymq = ym[(int64_t)pr.train * ny + pr.y];
+      for (int e = tid; e < CVL * PMAX; e += 256) (&sbeta[0][0])[e] = 0.0;
+      __syncthreads();
+      const int half = tid >> 7, t = tid & 127;
+#pragma unroll
+      for (int r = 0; r < CVL / 2; ++r) {
+        const int m = 2 * r + half;
+        double acc = 0.0;
+        if (m0 + m < nl)
+          acc = coef_row_terms(apath + ((int64_t)q * L + m0 + m) * p, (int64_t)pr.train * p, p,
+                               ysq, xm, xs, ju, t, 128,
+                               [&](int j, double bj) { sbeta[m][j] = bj; });
+        acc = wave_sum(acc);
+        if (lane == 0) sw[m][wid & 1] = acc;
+      }
+      __syncthreads();
+      if (tid < CVL) {
+        double s = 0.0;                    // block_sum<1> of a 128-thread block
+        for (int w = 0; w < 2; ++w) s += sw[tid][w];
+        sa0[tid] = ymq - s;
+      }
+      cvloss_chunk<true>(Gh, P, xcols, p, ones_col, yc, sbeta, sxc, snz, sred, nl, m0, L,
+                         cvraw + (int64_t)q * L, [&](int m) { return sa0[m]; });
+    }
+  } else {
+    f = (b - ncv) / L;
+    const int m = (b - ncv) % L;
+    ATE_DASSERT(f < nf);
+    const EnetProblem pr = probs[f];
+    double* out = coef + ((int64_t)f * L + m) * (p + 1);
+    if (m >= nlam_out[f]) {
+      for (int j = tid; j <= p; j += 256) st_out<true>(out + j, NAN);
+    } else {
+      const double ysq = ys[(int64_t)pr.train * ny + pr.y], ymq = ym[(int64_t)pr.train * ny + pr.y];
+      double acc = 0.0;
+      if (tid < 128)
+        acc = coef_row_terms(apath + ((int64_t)f * L + m) * p, (int64_t)pr.train * p, p, ysq, xm,
+                             xs, ju, tid, 128,
+                             [&](int j, double bj) { st_out<true>(out + 1 + j, bj); });
+      acc = wave_sum(acc);
+      if (lane == 0 && wid < 2) sw[0][wid] = acc;
+      __syncthreads();
+      if (tid == 0) {
+        double s = 0.0;
+        for (int w = 0; w < 2; ++w) s += sw[0][w];
+        st_out<true>(out, ymq - s);
+      }
+    }
+  }
+  // arrival: this workgroup's (written-through) stores have landed, then its count
+  wait_stores();
+  __syncthreads();
+  if (tid == 0) {
+    const int total = L + K * nch;
+    const int old = __hip_atomic_fetch_add(done + f, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ATE_DASSERT(old >= 0 && old < total);
+    slast = old == total - 1;
+  }
+  __syncthreads();
+  if (!slast) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  const bool bad = any_truncated(fnp, nfp);
+  if (wid == 0) {
+    int i0, i1;
+    cv_select_wave(cvraw, fold_probs, nfold, K, f, nlam_out, L, cvm, cvsd, sel, bad, lane, i0, i1);
+    if (lane == 0) { ssel[0] = i0; ssel[1] = i1; }
+  }
+  __syncthreads();
+  for (int which = 0; which < 2; ++which) {
+    double* out = which ? out_1se : out_min;
+    const int m = ssel[which];
+    ATE_DASSERT(m >= 0 && m < L);
+    for (int j = tid; j <= p; j += 256)
+      out[(int64_t)f * (p + 1) + j] = bad ? NAN : coef[((int64_t)f * L + m) * (p + 1) + j];
+  }
+}
+
+// probs / nlam_out / hold / ycol_of_prob: the path launch's nf + nfp problems (full problems
+// first); fold_probs[nf][K] (absolute problem indices) and nfold[nf][K] as ate_cv_select;
+// fold_npass: nlam-side pass counts of the nfp fold problems. Outputs: coef [nf][L][p+1],
+// cvraw [nf + nfp][L] (rows >= nf), cvm / cvsd [nf][L], sel [nf][2], out_min / out_1se
+// [nf][p+1]. done: nf int32, zero at launch.
+ATE_API int ate_enet_cv_tail(const void* G, int P, const void* hold, const void* xcols, int p,
+                             int ones_col, const void* ycol_of_prob, const void* apath,
+                             const void* probs, int ny, const void* nlam_out, const void* xm,
+                             const void* xs, const void* ju, const void* ym, const void* ys, int L,
+                             int nf, int nfp, int K, const void* fold_probs, const void* nfold,
+                             void* coef, void* cvraw, void* cvm, void* cvsd, void* sel,
+                             void* out_min, void* out_1se, const void* fold_npass, void* done,
+                             void* stream) {
+  if (p > PMAX || p < 1 || L > 256 || L < 1) return -1;
+  if (nf < 1 || K < 1 || nfp != nf * K) return -1;
+  const int nch = (L + CVL - 1) / CVL;
+  ATE_LAUNCH(enet_cv_tail_kernel, dim3(nfp * nch + nf * L), dim3(256), 0, (hipStream_t)stream,
+             (const double*)G, P, (const int*)hold, (const int*)xcols, p, ones_col,
+             (const int*)ycol_of_prob, (const double*)apath, (const EnetProblem*)probs, ny,
+             (const int*)nlam_out, (const double*)xm, (const double*)xs,
+             (const unsigned char*)ju, (const double*)ym, (const double*)ys, L, nf, nfp, K,
+             (const int*)fold_probs, (const double*)nfold, (double*)coef, (double*)cvraw,
+             (double*)cvm, (double*)cvsd, (int*)sel, (double*)out_min, (double*)out_1se,
+             (const int*)fold_npass, (int*)done);
   ATE_CHECK_LAUNCH();
   return 0;
 }

@@ -8,6 +8,7 @@
 // Inputs are fp64 score vectors or panel columns; rows with valid==0 (panel
 // padding) are skipped.
 #include "common.hpp"
+#include "dml_common.hpp"
 
 using namespace ate;
 
@@ -206,19 +207,7 @@ struct DmlMoments {
 // mode 1 (reference lm(Y_resid ~ 0 + W_resid), ate_functions.R:363-366):
 //   se = sqrt(RSS/(n-1)/S_ww).
 __global__ void dml_finalize_kernel(const double* __restrict__ m, int mode, double* __restrict__ res) {
-  double n = m[5];
-  double theta = m[0] / m[1];
-  double se;
-  if (mode == 0) {
-    double j = m[1] / n;
-    double psi2 = (m[2] - 2.0 * theta * m[3] + theta * theta * m[4]) / n;
-    se = sqrt(fmax(psi2, 0.0) / (j * j) / n);
-  } else {
-    double rss = m[6] - 2.0 * theta * m[0] + theta * theta * m[1];
-    se = sqrt(fmax(rss, 0.0) / (n - 1.0) / m[1]);
-  }
-  res[0] = theta;
-  res[1] = se;
+  dml_finalize_formula(m, mode, res);   // csrc/dml_common.hpp (shared with csrc/dml.hip)
 }
 
 ATE_API int ate_dml_moments(const void* yr, const void* wr, const void* valid, int64_t n,

@@ -15,7 +15,7 @@ from collections import defaultdict
 CLASSES = [("gram", r"gram_bf16_pair|gram_bf16_256|gram_bf16_kernel"),
            ("gram_reduce", r"gram_pair_reduce|slab_reduce|gram_.*reduce"),
            ("path", r"enet_path_kernel"),
-           ("cvloss", r"cvloss"),
+           ("cvloss", r"cvloss|enet_cv_tail"),
            ("resid", r"dml_resid"),
            ("prepare", r"enet_prep"),
            ("other", r".")]
