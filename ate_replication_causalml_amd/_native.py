@@ -66,8 +66,6 @@ c_double = ctypes.c_double
 _SIGS = {
     "ate_gram_bf16": "pliipipipipppp",
     "ate_gram_bf16_pair": "pllipippipippippiip",
-    "ate_gram_bf16_tri": "pllippipippipp",
-    "ate_gram_pair_bal": "",
     "ate_last_error": "pi",
     "ate_last_stale_error": "pi",
     "ate_clear_errors": "",
@@ -89,7 +87,6 @@ _SIGS = {
     "ate_dml_finalize": "pipp",
     "ate_boot_multinomial": "ppluiipp",
     "ate_boot_poisson": "ppluiilipp",
-    "ate_enet_isa_selftest": "pp",
     "ate_enet_prepare": "piipipiipipipppppppp",
     "ate_enet_prepare_fused": "piipipiipipi" + "ppppppp" + "plp",
     "ate_enet_path": "pipiippppidddipppppippp",

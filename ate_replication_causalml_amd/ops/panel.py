@@ -43,7 +43,7 @@ class DevicePanel:
     # 64-row blocked layout: data is [ld/64, P, 64], element (c, i) at
     # (i/64)*64*P + c*64 + i%64. One Gram K-step (64 rows x all P columns) is then one
     # contiguous 64*P*2-byte run of HBM instead of P runs of 128 bytes ld apart
-    # (profiles/r01_pmc/gram_diag.txt). Kernels that take (cs, bs) strides read both
+    # (profiles/r01_pmc). Kernels that take (cs, bs) strides read both
     # layouts; the others require column-major (``cm_ld`` raises).
     blocked: bool = False
     # exact (world-size-invariant) Gram: rows of every segment form blocks of this many

@@ -989,7 +989,7 @@ static void gbdt_hist_geom(int64_t n_train, int p, int d, int rule, int64_t* CH,
   }();
   // ~R rows per chunk (ATE_GBDT_HIST_ROWS; round 6, config-5 shard with the fused root, 10
   // trees: 16384 3.13-3.58 s, 32768 2.86, 65536 2.77-2.79, 131072 2.81-2.82, 262144
-  // 3.07-3.09; tools/r06_fused4.sh)
+  // 3.07-3.09; profiles/r06_cfg5)
   static const int64_t env_rows = [] {
     const char* e = getenv("ATE_GBDT_HIST_ROWS");
     return e ? (int64_t)std::max(1024, atoi(e)) : (int64_t)65536;
@@ -1007,7 +1007,7 @@ static void gbdt_hist_geom(int64_t n_train, int p, int d, int rule, int64_t* CH,
 static void gbdt_hist2_geom(int64_t n_train, int p, int64_t* CH, int64_t* nchunk, int64_t* nwg) {
   const int ydim2 = (p + FB2 - 1) / FB2;
   // ~R rows per chunk (ATE_GBDT_HIST2_ROWS; config-5 shard, 10 trees: 16384 3.05-3.46 s,
-  // 32768 2.905-2.914, 65536 2.874-2.879, 131072 2.889-2.894; tools/r06_fused3.sh)
+  // 32768 2.905-2.914, 65536 2.874-2.879, 131072 2.889-2.894; profiles/r06_cfg5)
   static const int64_t R = [] {
     const char* e = getenv("ATE_GBDT_HIST2_ROWS");
     return e ? (int64_t)std::max(1024, atoi(e)) : (int64_t)65536;

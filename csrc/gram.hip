@@ -130,18 +130,13 @@ __global__ __launch_bounds__(256) void gram_bf16_kernel(
 // SOURCE address (chunk (l&7)^(col&7) lands at position l&7) and undone on the read.
 constexpr int GT = 256;
 constexpr int GK = 64;
-#ifndef GRAM_CPOL
-#define GRAM_CPOL 0   // cache policy of the panel stream (2 = nt), A/B builds only
-#endif
 
 typedef const __attribute__((address_space(1))) char* gptr_t;   // a global-memory address
 __device__ __forceinline__ void glds16(gptr_t src, bf16_t* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(lds_base), 16, 0,
-                                   GRAM_CPOL);
+  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(lds_base), 16, 0, 0);
 }
 __device__ __forceinline__ void glds16(const void* src, bf16_t* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(lds_base), 16, 0,
-                                   GRAM_CPOL);
+  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(lds_base), 16, 0, 0);
 }
 
 __global__ __launch_bounds__(512) void gram_bf16_256_kernel(
@@ -234,46 +229,9 @@ __global__ __launch_bounds__(512) void gram_bf16_256_kernel(
 // hits L2 on what the other fetched). Every wave writes its 16x16 blocks contiguously
 // into a 272-block slab slot; a host-built table maps slab blocks to Gram blocks.
 constexpr int PAIR_SLOTS = 272;
-#ifndef GRAM_NSTAGE
-// > 2 (or GRAM_RING=1): the paired-tile K-loop runs a ring of GRAM_NSTAGE stages of 32 rows
-// (NSTAGE - 1 of them in flight while one is multiplied) instead of two 64-row stages (one
-// in flight). Measured slower (profiles/r05_gram_ring): A/B builds only.
-#define GRAM_NSTAGE 2
-#endif
-#ifndef GRAM_RING
-#define GRAM_RING (GRAM_NSTAGE > 2)
-#endif
-constexpr int PKS = GRAM_RING ? 32 : GK;                     // rows per stage
-constexpr int PNS = GRAM_NSTAGE;                             // stages in the ring
-constexpr int PAIR_LDS = PNS * 2 * GT * PKS;                 // bf16 elements
-static_assert(PAIR_LDS * 2 <= 160 * 1024, "paired-tile LDS ring exceeds 160 KB");
-
-// s_waitcnt vmcnt(n) for a runtime n <= 15 (expcnt / lgkmcnt not waited on)
-__device__ __forceinline__ void wait_vmcnt(int n) {
-  switch (n) {
-#define WV(k) case k: __builtin_amdgcn_s_waitcnt(0x0F70 | k); break;
-    WV(0) WV(1) WV(2) WV(3) WV(4) WV(5) WV(6) WV(7)
-    WV(8) WV(9) WV(10) WV(11) WV(12) WV(13) WV(14) WV(15)
-#undef WV
-    default: __builtin_amdgcn_s_waitcnt(0x0F70); break;
-  }
-}
-#ifndef GRAM_CROSS
-// 1: the two workgroups of a chunk issue a stage's 64 LDS-DMA pieces in crossed orders
-// (type-1 wave w issues what type-0 wave (w+4)%8 issues), so the pair never requests the same
-// line at the same moment; tools/hbm_stream.hip: a paired stream 4.5 -> 5.3 TB/s of unique
-// bytes. 2: type 1 issues its B pieces before its A pieces instead. 0: same order.
-// In the Gram itself neither changed anything (tile kernel 2.63 / 2.62 / 2.69 ms for 1 / 0 /
-// 2, bench step 3.81 / 3.83, profiles/r02c_gram/ab_cross.log): kept as an option, default 0.
-#define GRAM_CROSS 0
-#endif
-#ifndef GRAM_PRELOAD
-// 1: both 32-row halves' fragments of a stage are read before its MFMAs, the second half's
-// reads interleaved one per MFMA of the first (sched_group_barrier): one LDS wait per half
-// instead of one per 8 MFMAs. Tile kernel 2.59-2.62 -> 2.55-2.59 ms, same bits
-// (profiles/r05_gram_sync)
-#define GRAM_PRELOAD 1
-#endif
+constexpr int PAIR_LDS = 2 * 2 * GT * GK;   // bf16 elements: two stages of an A and a B image
+// Variants measured and not kept (a ring of 32-row stages, crossed issue orders, a
+// non-temporal panel stream, balanced 34-block roles, a split-triangle kernel): profiles/.
 #ifndef GRAM_PRIO
 // s_setprio 1 for waves 4-7 of the paired-tile kernel (see gram_bf16_pair_kernel):
 // 1 = in every workgroup, 2 = in diagonal-pair workgroups only (their waves 4-7 are the
@@ -281,35 +239,19 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 // box: none 2.66-2.67, 1: 2.60, 2: 2.57 ms, same bits (profiles/r05_gram_sync)
 #define GRAM_PRIO 2
 #endif
-#ifndef GRAM_DIAG
-#define GRAM_DIAG 0   // timing-only builds (tools/gram_diag.py): 1 = no MFMA work, 2 = no DMA,
-                      // 3 = 1 with only the off-diagonal tile's workgroups (each K-step
-                      // loaded once), 4 = normal work on the off-diagonal tiles only,
-                      // 5 = no per-stage barrier (wrong results; the cost of the stage
-                      // hand-off between the 8 waves: 2.66 -> 1.90 ms, profiles/r05_gram_sync)
-#endif
 
 __device__ __forceinline__ int tri_index(int m, int n) {   // m <= n < 8, row-major triangle
   return m * 8 - (m * (m - 1)) / 2 + (n - m);
 }
 
-#ifndef GRAM_BAL
-// 1: the diagonal-pair workgroup's eight waves hold 34 blocks each instead of 32 (rectangle)
-// and 36 (triangle): each triangle wave's last two blocks, (6, 7) and (7, 7) of its 8-block
-// triangle, move to the rectangle wave of the same region and half, which already holds
-// both fragments (half 0: A fragments 6, 7; half 1: B fragments 2, 3 = blocks 14, 15). Every
-// block still sums the same K sequence: the Gram bits do not change.
-#define GRAM_BAL 0
-#endif
 constexpr int PAIR_RECT = 0, PAIR_RECT_D0 = 1, PAIR_TRI = 2, PAIR_RECT_D1 = 3;
 template <int MODE> struct PairRole {
   static constexpr bool TRI = MODE == PAIR_TRI;
-  static constexpr int NB = MODE == PAIR_RECT ? 32 : GRAM_BAL ? 34 : TRI ? 36 : 32;
+  static constexpr int NB = TRI ? 36 : 32;
 };
 
-// The MFMAs of one 32-deep k-step of a wave role: a rectangle (8 A x 4 B fragments, plus the
-// two balanced-away triangle blocks in a diagonal-pair workgroup) or a triangle (8 fragments
-// as A and B, blocks m <= n in tri_index order, the last two dropped under GRAM_BAL).
+// The MFMAs of one 32-deep k-step of a wave role: a rectangle (8 A x 4 B fragments) or a
+// triangle (8 fragments as A and B, blocks m <= n in tri_index order).
 template <int MODE>
 __device__ __forceinline__ void pair_mfma(f32x4* acc, const bf16x8* af, const bf16x8* bfr) {
   if constexpr (MODE != PAIR_TRI) {
@@ -319,22 +261,13 @@ __device__ __forceinline__ void pair_mfma(f32x4* acc, const bf16x8* af, const bf
       for (int n = 0; n < 4; ++n)
         acc[m * 4 + n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m], bfr[n], acc[m * 4 + n],
                                                                  0, 0, 0);
-    if constexpr (GRAM_BAL && MODE == PAIR_RECT_D0) {
-      acc[32] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[6], af[7], acc[32], 0, 0, 0);
-      acc[33] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[7], af[7], acc[33], 0, 0, 0);
-    }
-    if constexpr (GRAM_BAL && MODE == PAIR_RECT_D1) {
-      acc[32] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[2], bfr[3], acc[32], 0, 0, 0);
-      acc[33] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[3], bfr[3], acc[33], 0, 0, 0);
-    }
   } else {
 #pragma unroll
     for (int m = 0; m < 8; ++m)
 #pragma unroll
       for (int n = m; n < 8; ++n)
-        if (tri_index(m, n) < PairRole<MODE>::NB)
-          acc[tri_index(m, n)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[m], af[n], acc[tri_index(m, n)], 0, 0, 0);
+        acc[tri_index(m, n)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            af[m], af[n], acc[tri_index(m, n)], 0, 0, 0);
   }
 }
 
@@ -384,73 +317,14 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
                                           int b0, bool haveB, bool idle, int abuf, int bbuf,
                                           int arow0, int bcol0, const Chunk& ch,
                                           bf16_t* lds_raw, float* __restrict__ out,
-                                          bool second, const uint8_t* __restrict__ X8) {
+                                          const uint8_t* __restrict__ X8) {
   constexpr bool TRI = PairRole<MODE>::TRI;
   constexpr int NB = PairRole<MODE>::NB;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   f32x4 acc[NB];
 #pragma unroll
   for (int i = 0; i < NB; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if GRAM_RING
-  // ---- ring of PNS stages of PKS = 32 rows: LDS image [stage][A|B][column][32 rows], four
-  // 16-byte pieces per column, piece p stored at slot p ^ ((col >> 1) & 3) (8 consecutive
-  // lanes of a fragment read hit 8 distinct 16-byte bank groups)
-  (void)second;
-  (void)X8;   // one-byte columns: the double-buffered path only
-  auto buf = [&](int st, int side) { return lds_raw + (st * 2 + side) * (GT * PKS); };
-  auto stage = [&](int st, int64_t i0) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int q = wid * 2 + r;                       // 16-column group
-      const int col = q * 16 + (lane >> 2);
-      const int pc = (lane & 3) ^ ((col >> 1) & 3);    // piece this lane fetches
-      const bf16_t* Xk = X + (i0 >> 6) * bs + (i0 & 63) + pc * 8;
-      glds16(Xk + (int64_t)(a0 + col) * cs, buf(st, 0) + q * 16 * PKS);
-      if (haveB) glds16(Xk + (int64_t)(b0 + col) * cs, buf(st, 1) + q * 16 * PKS);
-    }
-  };
-  auto frag = [&](const bf16_t* P_, int col, int cc) {
-    return *reinterpret_cast<const bf16x8*>(&P_[col * PKS + ((cc ^ ((col >> 1) & 3)) << 3)]);
-  };
-  const int per = haveB ? 4 : 2;                        // LDS-DMA loads per thread per stage
-  const int64_t nsteps = (ch.row1 - ch.row0) / PKS;
-  for (int j = 0; j < PNS - 1; ++j)
-    if (j < nsteps) stage(j, ch.row0 + j * PKS);
-  for (int64_t s = 0; s < nsteps; ++s) {
-    // stage s landed: at most the later stages' loads are outstanding
-    const int64_t later = nsteps - 1 - s < PNS - 2 ? nsteps - 1 - s : PNS - 2;
-    wait_vmcnt((int)later * per);
-    // ... in every wave; stage s-1 consumed. A raw s_barrier: __syncthreads()'s fence would
-    // drain every LDS-DMA in flight (the later stages' too) and undo the ring (round 6: the
-    // rings measured in round 5 had that drain)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (s + PNS - 1 < nsteps) stage((int)((s + PNS - 1) % PNS), ch.row0 + (s + PNS - 1) * PKS);
-    const int cur = (int)(s % PNS);
-    const bf16_t* As = buf(cur, abuf);
-    const bf16_t* Bs = buf(cur, bbuf);
-    if (!idle) {
-      const int cc = lane >> 4;
-      if constexpr (!TRI) {
-        bf16x8 af[8], bfr[4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) af[m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
-#pragma unroll
-        for (int n = 0; n < 4; ++n) bfr[n] = frag(Bs, bcol0 + n * 16 + (lane & 15), cc);
-        pair_mfma<MODE>(acc, af, bfr);
-      } else {
-        bf16x8 fr[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) fr[m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
-        pair_mfma<MODE>(acc, fr, fr);
-      }
-    }
-  }
-#else
   bf16_t (*lds)[2][GT * GK] = reinterpret_cast<bf16_t (*)[2][GT * GK]>(lds_raw);
-  // which 8-column pieces this wave copies (any wave may copy any piece: the LDS image only
-  // depends on q); `second` = the chunk's type-1 workgroup
-  const int qw = (GRAM_CROSS == 1 && second) ? ((wid + 4) & 7) : wid;
-  const bool bfirst = GRAM_CROSS == 2 && second && haveB;
   // SADDR (the schedules other than lockstep): every piece's address is a wave-uniform base
   // plus ONE per-lane byte offset -- lane l of a piece reads chunk (l & 7) ^ (l >> 3) of column
   // l >> 3 of its 8 columns, whichever piece it is -- so the copies need one address register
@@ -460,7 +334,6 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
   const uint32_t voff8_ = (uint32_t)((lane >> 2) * GK + (((lane & 3) ^ ((lane >> 3) & 2)) << 4));
   auto stage = [&](int st, int64_t i0) {
     if constexpr (SADDR) {
-      static_assert(!SADDR || GRAM_CROSS == 0, "crossed issue orders: lockstep schedule only");
       gptr_t Xk0 = (gptr_t) reinterpret_cast<const char*>(X + (i0 >> 6) * bs);
       // (opaque per stage: a sum of base and offset hoisted out of the K-loop would be a
       // 64-bit pointer per piece again)
@@ -515,13 +388,12 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int q = qw * 4 + r;
+      const int q = wid * 4 + r;
       const int col = q * 8 + (lane >> 3);
       const int cc = (lane & 7) ^ (col & 7);
       const bf16_t* Xk = X + (i0 >> 6) * bs + cc * 8;      // i0: multiple of GK = 64
-      if (bfirst) glds16(Xk + (int64_t)(b0 + col) * cs, &lds[st][1][q * 8 * GK]);
       glds16(Xk + (int64_t)(a0 + col) * cs, &lds[st][0][q * 8 * GK]);
-      if (haveB && !bfirst) glds16(Xk + (int64_t)(b0 + col) * cs, &lds[st][1][q * 8 * GK]);
+      if (haveB) glds16(Xk + (int64_t)(b0 + col) * cs, &lds[st][1][q * 8 * GK]);
     }
   };
   auto frag = [&](const bf16_t* P_, int col, int cc) {
@@ -538,16 +410,11 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
     const int slot = (lane >> 4) ^ ((cb >> 1) & 2);
     return *reinterpret_cast<const uint4*>(b8 + cb * GK + slot * 16);
   };
-  auto frag8 = [&](const bf16_t* P_, int col, int cc) {
-    const uint4 w = raw16(P_, col);
-    return bytes_to_bf16x8(cc >= 4 ? make_uint2(w.z, w.w) : make_uint2(w.x, w.y));
-  };
   const int64_t nsteps = (ch.row1 - ch.row0) / GK;
   if (nsteps > 0) stage(0, ch.row0);
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
   __syncthreads();
   // LATE: half 1 of the stage before (zeros ahead of stage 0: they add +0 to the +0 sums)
-  static_assert(!LATE || GRAM_PRELOAD, "the stagger schedule builds on the preload schedules");
   bf16x8 ha[LATE ? 8 : 1], hb[LATE && !TRI ? 4 : 1];
   if constexpr (LATE) {
 #pragma unroll
@@ -557,7 +424,6 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
       for (int n = 0; n < 4; ++n) hb[n] = bf16x8{};
     }
   }
-  const bool work = !idle && GRAM_DIAG != 1 && GRAM_DIAG != 3;
   for (int64_t s = 0; s < nsteps; ++s) {
     const int cur = s & 1;
     const bf16_t* As = lds[cur][abuf];
@@ -567,7 +433,7 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
       bf16x8 na[8], nb[TRI ? 1 : 4];
       uint4 raw[BY ? (TRI ? 8 : 4) : 1];
       const int c0 = lane >> 4, c1 = 4 + (lane >> 4);
-      if (work) {
+      if (!idle) {
         if constexpr (BY && !TRI) {
 #pragma unroll
           for (int n = 0; n < 4; ++n) raw[n] = raw16(Bs, bcol0 + n * 16 + (lane & 15));
@@ -623,11 +489,9 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
         }
       }
       // ... the copies of stage s+1 behind those MFMAs ...
-#if GRAM_DIAG != 2
       if (s + 1 < nsteps) stage(cur ^ 1, ch.row0 + (s + 1) * GK);
-#endif
       // ... and half 0 of stage s beside the reads of its half 1 into the registers just freed
-      if (work) {
+      if (!idle) {
         if constexpr (BY && !TRI) {
 #pragma unroll
           for (int m = 0; m < 8; ++m) ha[m] = frag(As, arow0 + m * 16 + (lane & 15), c1);
@@ -688,141 +552,110 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
         }
       }
     } else {
-#if GRAM_DIAG != 2
-    if (s + 1 < nsteps) stage(cur ^ 1, ch.row0 + (s + 1) * GK);
-#endif
-#if GRAM_PRELOAD
-    // every fragment of the stage (both 32-row halves) read from LDS up front, then the
-    // MFMAs: the waits on LDS leave the MFMA chains of the stage
-    if (!idle && GRAM_DIAG != 1 && GRAM_DIAG != 3) {
-      if constexpr (BY && !TRI) {
-        // byte B fragments: one 16-byte read per column holds both halves' rows, converted
-        // per half just ahead of its MFMAs; the second half's conversion interleaved with the
-        // first half's MFMAs (mask 0x002 VALU)
-        bf16x8 af[2][8];
-        uint4 braw[4];
+      if (s + 1 < nsteps) stage(cur ^ 1, ch.row0 + (s + 1) * GK);
+      // every fragment of the stage (both 32-row halves) read from LDS up front, then the
+      // MFMAs: the waits on LDS leave the MFMA chains of the stage
+      if (!idle) {
+        if constexpr (BY && !TRI) {
+          // byte B fragments: one 16-byte read per column holds both halves' rows, converted
+          // per half just ahead of its MFMAs; the second half's conversion interleaved with the
+          // first half's MFMAs (mask 0x002 VALU)
+          bf16x8 af[2][8];
+          uint4 braw[4];
 #pragma unroll
-        for (int n = 0; n < 4; ++n) braw[n] = raw16(Bs, bcol0 + n * 16 + (lane & 15));
+          for (int n = 0; n < 4; ++n) braw[n] = raw16(Bs, bcol0 + n * 16 + (lane & 15));
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int cc = kk * 4 + (lane >> 4);
+          for (int kk = 0; kk < 2; ++kk) {
+            const int cc = kk * 4 + (lane >> 4);
 #pragma unroll
-          for (int m = 0; m < 8; ++m) af[kk][m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
-        }
-        bf16x8 b0v[4], b1v[4];
+            for (int m = 0; m < 8; ++m) af[kk][m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
+          }
+          bf16x8 b0v[4], b1v[4];
 #pragma unroll
-        for (int n = 0; n < 4; ++n) b0v[n] = bytes_to_bf16x8(make_uint2(braw[n].x, braw[n].y));
+          for (int n = 0; n < 4; ++n) b0v[n] = bytes_to_bf16x8(make_uint2(braw[n].x, braw[n].y));
 #pragma unroll
-        for (int n = 0; n < 4; ++n) b1v[n] = bytes_to_bf16x8(make_uint2(braw[n].z, braw[n].w));
-        pair_mfma<MODE>(acc, af[0], b0v);
-        pair_mfma<MODE>(acc, af[1], b1v);
-        __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);     // B (both halves) + A half 0
-        __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);     // half 0 conversion
+          for (int n = 0; n < 4; ++n) b1v[n] = bytes_to_bf16x8(make_uint2(braw[n].z, braw[n].w));
+          pair_mfma<MODE>(acc, af[0], b0v);
+          pair_mfma<MODE>(acc, af[1], b1v);
+          __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);     // B (both halves) + A half 0
+          __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);     // half 0 conversion
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {                           // A half 1 reads beside
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // half 0's MFMAs
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
+          for (int i = 0; i < 8; ++i) {                           // A half 1 reads beside
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // half 0's MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {                          // half 1 conversion beside
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // the next MFMAs
-          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 24, 0);
-      } else if constexpr (BY) {
-        uint4 fraw[8];
+          for (int i = 0; i < 16; ++i) {                          // half 1 conversion beside
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // the next MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 24, 0);
+        } else if constexpr (BY) {
+          uint4 fraw[8];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) fraw[m] = raw16(As, arow0 + m * 16 + (lane & 15));
-        bf16x8 f0[8], f1[8];
+          for (int m = 0; m < 8; ++m) fraw[m] = raw16(As, arow0 + m * 16 + (lane & 15));
+          bf16x8 f0[8], f1[8];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) f0[m] = bytes_to_bf16x8(make_uint2(fraw[m].x, fraw[m].y));
+          for (int m = 0; m < 8; ++m) f0[m] = bytes_to_bf16x8(make_uint2(fraw[m].x, fraw[m].y));
 #pragma unroll
-        for (int m = 0; m < 8; ++m) f1[m] = bytes_to_bf16x8(make_uint2(fraw[m].z, fraw[m].w));
-        pair_mfma<MODE>(acc, f0, f0);
-        pair_mfma<MODE>(acc, f1, f1);
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);      // both halves' reads
-        __builtin_amdgcn_sched_group_barrier(0x002, 32, 0);     // half 0 conversion
+          for (int m = 0; m < 8; ++m) f1[m] = bytes_to_bf16x8(make_uint2(fraw[m].z, fraw[m].w));
+          pair_mfma<MODE>(acc, f0, f0);
+          pair_mfma<MODE>(acc, f1, f1);
+          __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);      // both halves' reads
+          __builtin_amdgcn_sched_group_barrier(0x002, 32, 0);     // half 0 conversion
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {                          // half 1 conversion beside
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // half 0's MFMAs
-          __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 16, 0);
-      } else if constexpr (!TRI) {
-        bf16x8 af[2][8], bfr[2][4];
+          for (int i = 0; i < 16; ++i) {                          // half 1 conversion beside
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // half 0's MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 16, 0);
+        } else if constexpr (!TRI) {
+          bf16x8 af[2][8], bfr[2][4];
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int cc = kk * 4 + (lane >> 4);
+          for (int kk = 0; kk < 2; ++kk) {
+            const int cc = kk * 4 + (lane >> 4);
 #pragma unroll
-          for (int m = 0; m < 8; ++m) af[kk][m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
+            for (int m = 0; m < 8; ++m) af[kk][m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
 #pragma unroll
-          for (int n = 0; n < 4; ++n) bfr[kk][n] = frag(Bs, bcol0 + n * 16 + (lane & 15), cc);
-        }
+            for (int n = 0; n < 4; ++n) bfr[kk][n] = frag(Bs, bcol0 + n * 16 + (lane & 15), cc);
+          }
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) pair_mfma<MODE>(acc, af[kk], bfr[kk]);
-        // schedule: the first half's 12 reads, then the second half's 12 reads one per
-        // MFMA of the first half, then the remaining MFMAs (mask 0x100 DS read, 0x008 MFMA)
-        __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
+          for (int kk = 0; kk < 2; ++kk) pair_mfma<MODE>(acc, af[kk], bfr[kk]);
+          // schedule: the first half's 12 reads, then the second half's 12 reads one per
+          // MFMA of the first half, then the remaining MFMAs (mask 0x100 DS read, 0x008 MFMA)
+          __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
 #pragma unroll
-        for (int i = 0; i < 12; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 12, 0);
-      } else {
-        bf16x8 fr[2][8];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int cc = kk * 4 + (lane >> 4);
-#pragma unroll
-          for (int m = 0; m < 8; ++m) fr[kk][m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) pair_mfma<MODE>(acc, fr[kk], fr[kk]);
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 8, 0);
-      }
-    }
-#else
-    if (!idle && GRAM_DIAG != 1 && GRAM_DIAG != 3) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int cc = kk * 4 + (lane >> 4);
-        if constexpr (!TRI) {
-          bf16x8 af[8], bfr[4];
-#pragma unroll
-          for (int m = 0; m < 8; ++m) af[m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
-#pragma unroll
-          for (int n = 0; n < 4; ++n)
-            bfr[n] = BY ? frag8(Bs, bcol0 + n * 16 + (lane & 15), cc)
-                        : frag(Bs, bcol0 + n * 16 + (lane & 15), cc);
-          pair_mfma<MODE>(acc, af, bfr);
+          for (int i = 0; i < 12; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 12, 0);
         } else {
-          bf16x8 fr[8];
+          bf16x8 fr[2][8];
 #pragma unroll
-          for (int m = 0; m < 8; ++m)
-            fr[m] = BY ? frag8(As, arow0 + m * 16 + (lane & 15), cc)
-                       : frag(As, arow0 + m * 16 + (lane & 15), cc);
-          pair_mfma<MODE>(acc, fr, fr);
+          for (int kk = 0; kk < 2; ++kk) {
+            const int cc = kk * 4 + (lane >> 4);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) fr[kk][m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
+          }
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) pair_mfma<MODE>(acc, fr[kk], fr[kk]);
+          __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 8, 0);
         }
       }
-    }
-#endif
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): next stage landed
-#if GRAM_DIAG != 5
     __syncthreads();
-#endif
   }
   if constexpr (LATE) {
-    if (work) pair_mfma<MODE>(acc, ha, TRI ? ha : hb);      // half 1 of the last stage
+    if (!idle) pair_mfma<MODE>(acc, ha, TRI ? ha : hb);      // half 1 of the last stage
   }
-#endif
   if (idle) return;
   // Slab block image is lane-major: float4 `lane` holds acc regs r = 0..3 = (row (l>>4)*4+r,
   // col l&15) of the 16x16 block, so each block is ONE 1-KB dwordx4 store per wave (4x fewer
@@ -846,14 +679,14 @@ extern "C" __attribute__((visibility("default"))) int ate_gram_clock_reset() {
 }
 #endif
 
-// SCHED: the K-loop schedule (SCHED_*; the ring build has one). prio: s_setprio 1 for waves
-// 4-7 (0 = none, 1 = every workgroup, 2 = diagonal-pair workgroups only; GRAM_PRIO).
+// SCHED: the K-loop schedule (SCHED_*). prio: s_setprio 1 for waves 4-7 (0 = none, 1 = every
+// workgroup, 2 = diagonal-pair workgroups only; GRAM_PRIO).
 template <bool BYTES, int SCHED>
 __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
     const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int4* __restrict__ tiles, int ntiles,
     const Chunk* __restrict__ chunks, int nchunks, float* __restrict__ slab,
     const uint8_t* __restrict__ X8, int prio) {
-  __shared__ __attribute__((aligned(16))) bf16_t lds[PAIR_LDS];   // 128 KB (ring: up to 160)
+  __shared__ __attribute__((aligned(16))) bf16_t lds[PAIR_LDS];   // 128 KB
 #ifdef GRAM_CLOCK
   const unsigned long long gc0 = clock64(), gw0 = wall_clock64();
 #endif
@@ -866,9 +699,6 @@ __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
   // row chunks are whole K-steps of one segment; tiles name 256-column blocks a <= b
   ATE_DASSERT(ch.row0 >= 0 && ch.row0 <= ch.row1 && ch.row0 % GK == 0 && ch.row1 % GK == 0);
   ATE_DASSERT(tl.x >= 0 && tl.y >= tl.x && type >= 0 && type <= 2);
-#if GRAM_DIAG >= 3
-  if (type != 0) return;
-#endif
   const bool haveB = type != 2;
   const int a0 = tl.x * GT, b0 = tl.y * GT;
   const int wid = threadIdx.x >> 6;
@@ -882,7 +712,7 @@ __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
   else { arow0 = half * 128; bcol0 = half * 128; }
   const int abuf = type == 0 ? 0 : region;
   const int bbuf = type == 0 ? 1 : region;
-  constexpr int RS = PairRole<PAIR_RECT_D0>::NB, TS = PairRole<PAIR_TRI>::NB;  // 34 / 34 (32 / 36)
+  constexpr int RS = PairRole<PAIR_RECT_D0>::NB, TS = PairRole<PAIR_TRI>::NB;  // 32 / 36
   const int base = type == 0 ? wid * 32 : tri ? 4 * RS + (wid - 4) * TS : wid * RS;
   float* out = slab + ((int64_t)c * ntiles + t) * (PAIR_SLOTS * 256) + (int64_t)base * 256;
   // the second-dispatched half (waves 4-7: the triangle waves of a diagonal pair, the
@@ -897,9 +727,9 @@ __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
   ATE_DASSERT(!BYTES || (X8 != nullptr && ntiles == 2 && b0 == 256));
   // waves 4-7 (the triangle waves of a diagonal pair, half of the rectangle waves of an
   // off-diagonal tile) are the late ones of the stagger schedule
-  constexpr bool STAG = (SCHED & SCHED_STAGGER) != 0 && !GRAM_RING;
+  constexpr bool STAG = (SCHED & SCHED_STAGGER) != 0;
 #define PAIR_WAVE(M, B, L) pair_wave<M, BYTES, B, L, SCHED != SCHED_LOCKSTEP>(                      \
-      X, cs, bs, a0, b0, haveB, idle, abuf, bbuf, arow0, bcol0, ch, lds, out, type != 0, X8)
+      X, cs, bs, a0, b0, haveB, idle, abuf, bbuf, arow0, bcol0, ch, lds, out, X8)
 #define PAIR_WAVE_BY(M, L) do { if (by) PAIR_WAVE(M, BYTES, L); else PAIR_WAVE(M, false, L); } while (0)
   if (tri) PAIR_WAVE_BY(PAIR_TRI, STAG);
   else if (type == 0) {
@@ -918,214 +748,6 @@ __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
     atomicAdd(&gram_clock[2], 1ull);
   }
 #endif
-}
-
-// ------------------------------------------------------------------ bf16 split-triangle kernel
-// P == 512 (32 column blocks of 16). Two workgroups per row chunk, both on one XCD:
-//   type 0 ("T"): stages columns 0..351 (22 blocks) and computes the upper triangle of blocks
-//                 I <= J < 22 (253 blocks);
-//   type 1 ("R"): stages all 512 columns and computes every block with J >= 22 (rows 0..21 x
-//                 cols 22..31 and the triangle 22..31: 275 blocks).
-// The paired-tile kernel's two workgroups each stage all 512 columns (the second reader of
-// every byte hits L2 on the first one's fetch); here only 352 of them are read twice, so a
-// chunk moves 864 column-reads into LDS instead of 1024 (-16 %) for the same 528 blocks.
-// Each wave owns a fixed role (a rectangle of A x B blocks, a triangle, or the one mixed role),
-// described at compile time by its fragment columns and block list; roles hold <= 36 blocks.
-constexpr int TRI_SLOTS = 288;            // slab blocks per (chunk, workgroup): 8 waves x 36
-constexpr int TRI_SPLIT = 22;             // column blocks staged by the type-0 workgroup
-
-template <int NF> struct FragCols { int c[NF]; };
-template <int NB> struct BlockPairs { int a[NB], b[NB]; };
-
-// rect<A0, NA, B0, NB>: fragments A0.., then B0..; block m*NB + n = (A0 + m, B0 + n)
-template <int A0, int NA, int B0, int NB>
-struct RoleRect {
-  static constexpr int NF = NA + NB, NBK = NA * NB;
-  static constexpr FragCols<NF> fc() {
-    FragCols<NF> r{};
-    for (int f = 0; f < NF; ++f) r.c[f] = f < NA ? A0 + f : B0 + (f - NA);
-    return r;
-  }
-  static constexpr BlockPairs<NBK> bp() {
-    BlockPairs<NBK> r{};
-    for (int m = 0; m < NA; ++m)
-      for (int n = 0; n < NB; ++n) { r.a[m * NB + n] = m; r.b[m * NB + n] = NA + n; }
-    return r;
-  }
-};
-// tri<S0, S>: fragments S0..S0+S-1 serve as A and B; blocks (m, n), m <= n, row-major
-template <int S0, int S>
-struct RoleTri {
-  static constexpr int NF = S, NBK = S * (S + 1) / 2;
-  static constexpr FragCols<NF> fc() {
-    FragCols<NF> r{};
-    for (int f = 0; f < NF; ++f) r.c[f] = S0 + f;
-    return r;
-  }
-  static constexpr BlockPairs<NBK> bp() {
-    BlockPairs<NBK> r{};
-    int i = 0;
-    for (int m = 0; m < S; ++m)
-      for (int n = m; n < S; ++n) { r.a[i] = m; r.b[i] = n; ++i; }
-    return r;
-  }
-};
-// the mixed role of type 1: fragments 21..31; (21, 22..26), triangle 22..26, triangle 27..31
-struct RoleMix {
-  static constexpr int NF = 11, NBK = 35;
-  static constexpr FragCols<NF> fc() {
-    FragCols<NF> r{};
-    for (int f = 0; f < NF; ++f) r.c[f] = 21 + f;
-    return r;
-  }
-  static constexpr BlockPairs<NBK> bp() {
-    BlockPairs<NBK> r{};
-    int i = 0;
-    for (int n = 1; n <= 5; ++n) { r.a[i] = 0; r.b[i] = n; ++i; }
-    for (int g = 0; g < 2; ++g)
-      for (int m = 0; m < 5; ++m)
-        for (int n = m; n < 5; ++n) { r.a[i] = 1 + 5 * g + m; r.b[i] = 1 + 5 * g + n; ++i; }
-    return r;
-  }
-};
-
-// One wave's whole K-loop in its role. The workgroup stages NPC 8-column pieces (columns
-// 0 .. 8 NPC - 1) per 64-row stage by LDS-DMA, double buffered; every wave issues its share
-// of the pieces, computes the current stage, waits for its own pieces of the next one and
-// meets the others at the barrier. PRE: both 32-row halves' fragments read before the MFMAs
-// (only where registers allow: 4 NBK + 8 NF <= 224).
-template <class R, int NSTG>
-__device__ __forceinline__ void tri_role(const bf16_t* __restrict__ X, int64_t cs, int64_t bs,
-                                         const Chunk& ch, int npc, bf16_t* lds_raw,
-                                         float* __restrict__ out) {
-  constexpr int NF = R::NF, NBK = R::NBK;
-  constexpr FragCols<NF> FC = R::fc();
-  constexpr BlockPairs<NBK> BP = R::bp();
-  constexpr bool PRE = 4 * NBK + 8 * NF <= 224;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int stage_elems = npc * 8 * GK;
-  const int mine = (npc - wid + 7) >> 3;          // LDS-DMA pieces this wave issues per stage
-  f32x4 acc[NBK];
-#pragma unroll
-  for (int i = 0; i < NBK; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto stage = [&](int st, int64_t i0) {
-    bf16_t* dst = lds_raw + st * stage_elems;
-    const bf16_t* Xk = X + (i0 >> 6) * bs;
-    for (int q = wid; q < npc; q += 8) {
-      const int col = q * 8 + (lane >> 3);
-      const int cc = (lane & 7) ^ (col & 7);
-      glds16(Xk + (int64_t)col * cs + cc * 8, dst + q * 8 * GK);
-    }
-  };
-  auto frag = [&](const bf16_t* P_, int col, int cc) {
-    return *reinterpret_cast<const bf16x8*>(&P_[col * GK + ((cc ^ (col & 7)) << 3)]);
-  };
-  const int64_t nsteps = (ch.row1 - ch.row0) / GK;
-#pragma unroll
-  for (int j = 0; j < NSTG - 1; ++j)
-    if (j < nsteps) stage(j, ch.row0 + j * GK);
-  for (int64_t s = 0; s < nsteps; ++s) {
-    // stage s landed (this wave's pieces; at most the later stages' are outstanding), then
-    // the barrier: every wave's pieces of stage s landed, stage s - 1 consumed by every wave
-    // (raw s_barrier, not __syncthreads(): its fence would drain every LDS-DMA in flight,
-    // including the later stages'; lgkmcnt(0) retires this wave's reads of stage s - 1, whose
-    // buffer the DMA issued after the barrier overwrites)
-    if constexpr (NSTG > 2) {
-      const int64_t left = nsteps - 1 - s;
-      if (left > 0) wait_vmcnt((NSTG - 2) * mine);
-      else __builtin_amdgcn_s_waitcnt(0x0F70);
-    } else {
-      __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (s + NSTG - 1 < nsteps) stage((int)((s + NSTG - 1) % NSTG), ch.row0 + (s + NSTG - 1) * GK);
-    const bf16_t* S_ = lds_raw + (int)(s % NSTG) * stage_elems;
-    if constexpr (PRE) {
-      bf16x8 fr[2][NF];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int cc = kk * 4 + (lane >> 4);
-#pragma unroll
-        for (int f = 0; f < NF; ++f) fr[kk][f] = frag(S_, FC.c[f] * 16 + (lane & 15), cc);
-      }
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int b = 0; b < NBK; ++b)
-          acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[kk][BP.a[b]], fr[kk][BP.b[b]],
-                                                           acc[b], 0, 0, 0);
-      // the first half's reads, then the second half's reads one per MFMA of the first half
-      __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
-#pragma unroll
-      for (int i = 0; i < NF; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NBK - NF, 0);
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int cc = kk * 4 + (lane >> 4);
-        bf16x8 fr[NF];
-#pragma unroll
-        for (int f = 0; f < NF; ++f) fr[f] = frag(S_, FC.c[f] * 16 + (lane & 15), cc);
-#pragma unroll
-        for (int b = 0; b < NBK; ++b)
-          acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[BP.a[b]], fr[BP.b[b]], acc[b],
-                                                           0, 0, 0);
-      }
-    }
-  }
-  // lane-major 16x16 block images, one dwordx4 store per block (as the paired-tile kernel)
-#pragma unroll
-  for (int i = 0; i < NBK; ++i)
-    *reinterpret_cast<f32x4*>(out + i * 256 + lane * 4) = acc[i];
-}
-
-#ifndef GRAM_TRI_NSTG0
-// LDS stages of the type-0 workgroup (352 columns x 64 rows = 44 KB each): 3 = two stages in
-// flight while one is multiplied (132 KB); the type-1 workgroup's 64 KB stages fit only 2
-#define GRAM_TRI_NSTG0 3
-#endif
-constexpr int TRI_LDS = (GRAM_TRI_NSTG0 * TRI_SPLIT * 16 > 2 * 512 ? GRAM_TRI_NSTG0 * TRI_SPLIT * 16
-                                                                   : 2 * 512) * GK;
-
-__global__ __launch_bounds__(512) void gram_bf16_tri_kernel(
-    const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const Chunk* __restrict__ chunks,
-    int nchunks, float* __restrict__ slab) {
-  __shared__ __attribute__((aligned(16))) bf16_t lds[TRI_LDS];   // 128 / 132 KB
-  const int L = xcd_remap(blockIdx.x, gridDim.x);
-  const int c = L >> 1, type = L & 1;
-  ATE_DASSERT(c < nchunks);
-  const Chunk ch = chunks[c];
-  ATE_DASSERT(ch.row0 >= 0 && ch.row0 <= ch.row1 && ch.row0 % GK == 0 && ch.row1 % GK == 0);
-  const int wid = threadIdx.x >> 6;
-  float* out = slab + ((int64_t)c * 2 + type) * (TRI_SLOTS * 256) + (int64_t)wid * 36 * 256;
-  if (type == 0) {
-    constexpr int npc = TRI_SPLIT * 2;          // 352 columns = 44 pieces of 8
-    switch (wid) {
-      case 0: tri_role<RoleTri<0, 8>, GRAM_TRI_NSTG0>(X, cs, bs, ch, npc, lds, out); break;
-      case 1: tri_role<RoleTri<8, 8>, GRAM_TRI_NSTG0>(X, cs, bs, ch, npc, lds, out); break;
-      case 2: tri_role<RoleRect<0, 4, 8, 8>, GRAM_TRI_NSTG0>(X, cs, bs, ch, npc, lds, out); break;
-      case 3: tri_role<RoleRect<4, 4, 8, 8>, GRAM_TRI_NSTG0>(X, cs, bs, ch, npc, lds, out); break;
-      case 4: tri_role<RoleRect<0, 6, 16, 6>, GRAM_TRI_NSTG0>(X, cs, bs, ch, npc, lds, out); break;
-      case 5: tri_role<RoleRect<6, 5, 16, 6>, GRAM_TRI_NSTG0>(X, cs, bs, ch, npc, lds, out); break;
-      case 6: tri_role<RoleRect<11, 5, 16, 6>, GRAM_TRI_NSTG0>(X, cs, bs, ch, npc, lds, out); break;
-      default: tri_role<RoleTri<16, 6>, GRAM_TRI_NSTG0>(X, cs, bs, ch, npc, lds, out); break;
-    }
-  } else {
-    constexpr int npc = 64;                     // all 512 columns
-    switch (wid) {
-      case 0: tri_role<RoleRect<0, 7, 22, 5>, 2>(X, cs, bs, ch, npc, lds, out); break;
-      case 1: tri_role<RoleRect<7, 7, 22, 5>, 2>(X, cs, bs, ch, npc, lds, out); break;
-      case 2: tri_role<RoleRect<14, 7, 22, 5>, 2>(X, cs, bs, ch, npc, lds, out); break;
-      case 3: tri_role<RoleRect<0, 7, 27, 5>, 2>(X, cs, bs, ch, npc, lds, out); break;
-      case 4: tri_role<RoleRect<7, 7, 27, 5>, 2>(X, cs, bs, ch, npc, lds, out); break;
-      case 5: tri_role<RoleRect<14, 7, 27, 5>, 2>(X, cs, bs, ch, npc, lds, out); break;
-      case 6: tri_role<RoleRect<21, 6, 27, 5>, 2>(X, cs, bs, ch, npc, lds, out); break;
-      default: tri_role<RoleMix, 2>(X, cs, bs, ch, npc, lds, out); break;
-    }
-  }
 }
 
 // Exact (world-size-invariant) reduction: a chunk partial v is split into two int64 limbs
@@ -1221,7 +843,6 @@ __global__ void gram_pair_reduce_kernel(const float* __restrict__ slab, const in
       (const void*)(gram_bf16_pair_kernel<true, S>), "gram_bf16_pair_kernel<bytes, sched " #S ">", 512, 0);
 PAIR_SCHEDS(PAIR_SHAPE)
 #undef PAIR_SHAPE
-ATE_KERNEL_SHAPE("gram_bf16_tri_kernel", 512, 0, gram_bf16_tri_kernel)
 ATE_KERNEL_SHAPE("gram_bf16_256_kernel", 512, 0, gram_bf16_256_kernel)
 ATE_KERNEL_SHAPE("gram_bf16_kernel", 256, 0, gram_bf16_kernel)
 
@@ -1233,8 +854,7 @@ ATE_API int ate_gram_bf16_pair(const void* X, int64_t cs, int64_t bs, int P, con
                                const void* seg_chunk0, int nseg, void* slab, void* G, int what,
                                void* Gx, const void* X8, int sched, int prio, void* stream) {
   if (P % (2 * GT) || what < 1 || what > 3) return -1;
-  if (X8 != nullptr && (P != 512 || ntiles != 2 || GRAM_RING)) return -1;
-  if (GRAM_RING && sched != SCHED_LOCKSTEP) return -1;
+  if (X8 != nullptr && (P != 512 || ntiles != 2)) return -1;
   // the other schedules address a piece's 8 columns with a 32-bit per-lane byte offset
   if (sched != SCHED_LOCKSTEP && cs >= ((int64_t)1 << 28)) return -1;
   // the priority raise was tuned for lockstep; with the stagger it measures as no gain
@@ -1267,31 +887,6 @@ ATE_API int ate_gram_bf16_pair(const void* X, int64_t cs, int64_t bs, int P, con
                        (const float*)slab, (const int2*)blocks, ntiles, PAIR_SLOTS,
                        (const int*)seg_chunk0, nseg, P, (double*)G, (long long*)Gx,
                        X8 != nullptr ? PAIR_BYTE0 : P);
-    ATE_CHECK_LAUNCH();
-  }
-  return 0;
-}
-
-// The slab layout of the paired-tile kernel's diagonal-pair workgroups (ops/gram.py
-// _pair_tiles reads it): 1 = 34 blocks per wave (GRAM_BAL), 0 = 32 / 36.
-ATE_API int ate_gram_pair_bal() { return GRAM_BAL; }
-
-// Split-triangle Gram (P == 512): what as ate_gram_bf16_pair; blocks = [2][TRI_SLOTS] int2.
-ATE_API int ate_gram_bf16_tri(const void* X, int64_t cs, int64_t bs, int P, const void* blocks,
-                              const void* chunks, int nchunks, const void* seg_chunk0, int nseg,
-                              void* slab, void* G, int what, void* Gx, void* stream) {
-  if (P != 512 || what < 1 || what > 3) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  if (what & 1) {
-    ATE_LAUNCH(gram_bf16_tri_kernel, dim3(nchunks * 2), dim3(512), 0, s,
-                       (const bf16_t*)X, cs, bs, (const Chunk*)chunks, nchunks, (float*)slab);
-    ATE_CHECK_LAUNCH();
-  }
-  if (what & 2) {
-    const int64_t total = (int64_t)nseg * 2 * TRI_SLOTS * 256;
-    ATE_LAUNCH(gram_pair_reduce_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, s,
-                       (const float*)slab, (const int2*)blocks, 2, TRI_SLOTS,
-                       (const int*)seg_chunk0, nseg, P, (double*)G, (long long*)Gx, P);
     ATE_CHECK_LAUNCH();
   }
   return 0;

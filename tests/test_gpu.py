@@ -71,37 +71,6 @@ def test_gram_pair_kernel_vs_tile256(gpu, monkeypatch, p):
     assert torch.equal(G0, G0.transpose(1, 2))
 
 
-@pytest.mark.parametrize("blocked", [False, True])
-def test_gram_tri_kernel_vs_pair(gpu, monkeypatch, blocked):
-    """Split-triangle kernel (P == 512, csrc/gram.hip gram_bf16_tri_kernel) vs the paired-tile
-    kernel vs fp64, on a column-major and on a 64-row blocked panel; symmetric, every block
-    written once (the slab table covers the triangle: tests/test_gram_plan.py)."""
-    from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
-    if blocked:
-        pan = synthetic_panel(40000, p=480, folds=5, seed=5, dtype="bf16", blocked=True,
-                              device=gpu)
-    else:
-        rs = np.random.RandomState(5)
-        n = 7000
-        pan = build_panel(rs.randn(n, 400), rs.rand(n), rs.randint(0, 2, n),
-                          folds=rs.randint(0, 5, n), dtype="bf16", device=gpu)
-    assert pan.P == 512
-    gram_op._plan_cache.clear()
-    monkeypatch.setattr(gram_op, "GRAM_TRI", True)
-    assert gram_op.plan_for(pan).tri
-    Gt = gram_op.gram(pan).clone()
-    gram_op._plan_cache.clear()
-    monkeypatch.setattr(gram_op, "GRAM_TRI", False)
-    assert not gram_op.plan_for(pan).tri
-    Gp = gram_op.gram(pan).clone()
-    gram_op._plan_cache.clear()
-    ref = gram_op.gram_reference(pan).to(gpu)
-    scale = ref.abs().max()
-    assert ((Gt - ref).abs().max() / scale) < 2e-6
-    assert ((Gt - Gp).abs().max() / scale) < 2e-6
-    assert torch.equal(Gt, Gt.transpose(1, 2))
-
-
 def test_byte_columns_gram_same_bits(gpu, monkeypatch):
     """One-byte columns (data/device_dgp.synthetic_panel: the {0, 1} columns in physical
     columns 384..511 plus a byte copy; csrc/gram.hip streams the copy as bf16 halves and the
@@ -285,18 +254,6 @@ def test_enet_cv_kernels_vs_cpu(gpu):
                        atol=1e-6)
     assert torch.equal(rg.sel.cpu().long(), rc.sel.long())
     assert np.allclose(rg.cvm[0, :nl].cpu().numpy(), rc.cvm[0, :nl].numpy(), rtol=1e-6)
-
-
-def test_enet_cross_lane_primitives(gpu):
-    """csrc/enet.hip row_replicate (permlane32/16 swaps) and fmac_bcast (DPP64
-    row_newbcast), the broadcasts of the row-blocked lasso walk, on gfx950."""
-    out = torch.zeros(320, dtype=torch.float64, device=gpu)
-    _native.call("ate_enet_isa_selftest", out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    o = out.cpu().numpy()
-    lane = np.arange(64)
-    for r in range(4):
-        np.testing.assert_array_equal(o[r * 64:(r + 1) * 64], 16 * r + (lane & 15))
-    np.testing.assert_array_equal(o[256:], 1 + 2 * (16 * (lane >> 4) + 5))
 
 
 def test_enet_fold_wait_timeout_poisons_and_raises(gpu, monkeypatch):

@@ -1,8 +1,8 @@
 """Build an alternative kernel library for A/B timing: every in-tree object except one
 source file, which is recompiled with extra flags.
 
-  python tools/build_variant.py base enet.hip -DENET_BALLOT_ONLY=1
-    -> ate_replication_causalml_amd/_lib/libatehip_base.so  (select with ATE_HIP_LIB=...)
+  python tools/build_variant.py dense16 enet.hip -DENET_PULL_DENSE=16
+    -> ate_replication_causalml_amd/_lib/libatehip_dense16.so  (select with ATE_HIP_LIB=...)
   python tools/build_variant.py head build/r/enet.hip@HEAD   (a file written by git show;
     the name before '@' says which in-tree object it replaces)
 """

@@ -1,5 +1,5 @@
 """Run the bf16 Gram kernel alone on the N=1e7, p=500 bench panel (A/B of the 256-tile
-kernel variants, and for PMC profiling). Usage: gram_only.py [N] [tri|pair|tile256 ...];
+kernel variants, and for PMC profiling). Usage: gram_only.py [N] [pair|pair16|tile256 ...];
 pair and pair16 take a K-loop schedule suffix (pair:lockstep, pair:stagger: ops/gram.py
 SCHEDULES); ATE_BLOCKED=0 for a column-major panel"""
 import os
@@ -25,9 +25,7 @@ sched0 = gram_mod.GRAM_SCHED
 for name in variants:
     v, _, sched = name.partition(":")
     gram_mod.GRAM_SCHED = sched or sched0
-    # "tri": the split-triangle kernel (P == 512); "pair": the paired-tile kernel
-    gram_mod.GRAM_KERNEL = "pair" if v in ("tri", "pair16") else v
-    gram_mod.GRAM_TRI = v == "tri"
+    gram_mod.GRAM_KERNEL = "pair" if v == "pair16" else v
     gram_mod.BYTE_COLS = v != "pair16"      # pair16: the panel's byte columns read as bf16
     gram_mod._plan_cache.clear()
     for _ in range(3):

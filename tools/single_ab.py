@@ -1,7 +1,7 @@
 """A/B of the single ate_dml call (bench.py's timed step) over Gram kernels on ONE panel:
 the panel is generated once, each variant's step is captured and timed in alternation
 (K calls back to back, R rounds), so box-to-box and clock drift cancel out.
-Usage: single_ab.py [tri,pair] [rounds] [calls]   (variants: tri | pair | pair16, with
+Usage: single_ab.py [pair,pair16] [rounds] [calls]   (variants: pair | pair16, with
 optional suffixes :SCHED -- a K-loop schedule of ops/gram.py SCHEDULES, e.g. pair:lockstep,
 pair:stagger --, /pN -- s_setprio for waves 4-7: 0 none, 1 all, 2 diagonal pairs -- and @rN
 -- the paired Gram's plan built for N whole rounds of workgroups; in that order)"""
@@ -21,7 +21,7 @@ from ate_replication_causalml_amd.ops import gram as gram_mod  # noqa: E402
 from ate_replication_causalml_amd.parallel.comm import LocalComm  # noqa: E402
 from ate_replication_causalml_amd.utils.graphs import SegmentedStep  # noqa: E402
 
-variants = (sys.argv[1] if len(sys.argv) > 1 else "tri,pair").split(",")
+variants = (sys.argv[1] if len(sys.argv) > 1 else "pair,pair16").split(",")
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 calls = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 dev = torch.device("cuda", 0)
@@ -38,7 +38,6 @@ def _select(v):
     v, _, sched = v.partition(":")
     gram_mod.GRAM_SCHED = sched or _SCHED0
     gram_mod.GRAM_PRIO = int(prio) if prio else _PRIO0
-    gram_mod.GRAM_TRI = v == "tri"
     gram_mod.BYTE_COLS = v != "pair16"      # pair16: the byte columns read as bf16
     if r:
         os.environ["ATE_GRAM_ROUNDS"] = r
