@@ -104,6 +104,7 @@ _SIGS = {
     "ate_irm_scores": "ipllpipiipiiiiidipp",
     "ate_irm_sens_moments": "ipllpipiipiiiiidippp",
     "ate_irm_target_moments": "ipllpipiipiiiiidippp",
+    "ate_irm_score_link": "ii" + "ipllpipiipiiiiidippp",
     "ate_iivm_moments": "ipllpipiipiiiiiiidippp",
     "ate_group_boot": "pppliiuippp",
     "ate_group_boot_scratch": "iii",
@@ -116,6 +117,8 @@ _SIGS = {
     "ate_policy_search": "ppiilppp",
     "ate_lognet_path": "iplpiipipipdddippippppppppp",
     "ate_lognet_cvloss": "iplpiippipppipp",
+    "ate_lognet_path_groups": "iplpiipipipppdpdiippppppppp",
+    "ate_lognet_cvloss_set": "iplpiipipipppipp",
     "ate_dgp_fill": "iplllllp" + "uiipppp",
     "ate_sel_block_rows": "",
     "ate_sel_gen_count": "upilllpp",

@@ -242,18 +242,33 @@ def ate_dml(Y, W, X, folds=5, lambda_rule="min", method="DML cross-fit (LASSO)",
                                 method=method, device=run.device(), dtype=run.dtype)
 
 
+def _linear_only(propensity, what):
+    """``propensity`` of an estimator the binomial propensity fit does not reach."""
+    from .estimators.irm import check_propensity
+    if check_propensity(propensity) != "linear":
+        raise ValueError(f'propensity="logit" is not available for {what}: only the '
+                         'linear-probability propensity ("linear")')
+
+
 def ate_dml_irm(Y, W, X, folds=5, lambda_rule="min", clip=0.01,
                 method="DML-IRM cross-fit (LASSO)", run=None, repeats=1,
-                aggregate="median") -> AteResult:
+                aggregate="median", propensity="linear") -> AteResult:
     """K-fold cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1)
     with CV-LASSO nuisances: per-arm outcome regressions and the linear-probability
     propensity (clipped to [clip, 1 - clip]) on the fold Gram stack; the ATE under
     heterogeneous effects, doubly robust (estimators/irm.py). W must be binary.
     ``repeats`` > 1: repeated cross-fitting over that many K-fold partitions (at most
     ``folds``), ``aggregate`` "median" (default) or "mean", as ate_dml; the partitions share
-    one Gram pass and one fused score pass (estimators/irm.irm_repeated_phases)."""
+    one Gram pass and one fused score pass (estimators/irm.irm_repeated_phases).
+    ``propensity``: "linear" (default), or "logit" for the binomial CV-LASSO propensity
+    (cv.glmnet(family="binomial"), all K * K fits in one launch, the score through the
+    logistic link) -- as do ate_dml_irm_gate / _cate / _policy / _targets. Limits of "logit"
+    (ValueError): ``repeats`` = 1, no row shards, an fp32 / fp64 panel, p <= 96, K <= 16; not
+    available for ate_dml_irm_sensitivity and ate_dml_iivm."""
     run = _run(run)
     with trace("ate_dml_irm", folds=folds, repeats=repeats):
+        from .estimators.irm import check_logit_scope
+        check_logit_scope(propensity, X, folds, repeats=repeats)
         if repeats != 1:
             if _ref(run):
                 from .reference import estimators as R
@@ -266,14 +281,16 @@ def ate_dml_irm(Y, W, X, folds=5, lambda_rule="min", clip=0.01,
         if _ref(run):
             from .reference import estimators as R
             return R.dml_irm_lasso(Y, W, X, folds=folds, seed=run.seed, lambda_rule=lambda_rule,
-                                   clip=clip, method=method)
+                                   clip=clip, method=method, propensity=propensity)
         from .estimators import irm as DI
         return DI.dml_irm_lasso(Y, W, X, folds=folds, seed=run.seed, lambda_rule=lambda_rule,
-                                clip=clip, method=method, device=run.device(), dtype=run.dtype)
+                                clip=clip, method=method, device=run.device(), dtype=run.dtype,
+                                propensity=propensity)
 
 
 def ate_dml_irm_gate(Y, W, X, groups, folds=5, lambda_rule="min", clip=0.01, n_boot=999,
-                     level=0.95, method="DML-IRM group ATEs (LASSO)", run=None) -> GateResult:
+                     level=0.95, method="DML-IRM group ATEs (LASSO)", run=None,
+                     propensity="linear") -> GateResult:
     """Group average treatment effects of ate_dml_irm -- the mean AIPW score within each
     group of ``groups`` (an (n,) vector of labels; at most 64 groups) -- with pointwise and
     simultaneous ``level`` confidence bounds, the latter from ``n_boot`` Rademacher
@@ -284,17 +301,18 @@ def ate_dml_irm_gate(Y, W, X, groups, folds=5, lambda_rule="min", clip=0.01, n_b
             from .reference import estimators as R
             return R.dml_irm_gate(Y, W, X, groups, folds=folds, seed=run.seed,
                                   lambda_rule=lambda_rule, clip=clip, n_boot=n_boot, level=level,
-                                  method=method)
+                                  method=method, propensity=propensity)
         from .estimators import gate as DG
         return DG.dml_irm_gate_lasso(Y, W, X, groups, folds=folds, seed=run.seed,
                                      lambda_rule=lambda_rule, clip=clip, n_boot=n_boot,
                                      level=level, method=method, device=run.device(),
-                                     dtype=run.dtype)
+                                     dtype=run.dtype, propensity=propensity)
 
 
 def ate_dml_irm_cate(Y, W, X, by, df=5, degree=3, knots=None, grid=None, folds=5,
                      lambda_rule="min", clip=0.01, n_boot=999, level=0.95,
-                     method="DML-IRM CATE curve (LASSO)", run=None) -> CateResult:
+                     method="DML-IRM CATE curve (LASSO)", run=None,
+                     propensity="linear") -> CateResult:
     """The conditional average treatment effect of ate_dml_irm along one covariate ``by`` (a
     column index into X, or an (n,) vector): the projection of the AIPW score on a B-spline
     basis (``df`` <= 32 functions of ``degree`` 0..3, quantile knots unless ``knots`` is
@@ -308,17 +326,19 @@ def ate_dml_irm_cate(Y, W, X, by, df=5, degree=3, knots=None, grid=None, folds=5
             from .reference import estimators as R
             return R.dml_irm_cate(Y, W, X, by, df=df, degree=degree, knots=knots, grid=grid,
                                   n_boot=n_boot, level=level, folds=folds, seed=run.seed,
-                                  lambda_rule=lambda_rule, clip=clip, method=method)
+                                  lambda_rule=lambda_rule, clip=clip, method=method,
+                                  propensity=propensity)
         from .estimators import cate as DC
         return DC.dml_irm_cate_lasso(Y, W, X, by, df=df, degree=degree, knots=knots, grid=grid,
                                      n_boot=n_boot, level=level, folds=folds, seed=run.seed,
                                      lambda_rule=lambda_rule, clip=clip, method=method,
-                                     device=run.device(), dtype=run.dtype)
+                                     device=run.device(), dtype=run.dtype, propensity=propensity)
 
 
 def ate_dml_irm_policy(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.0, train=None,
                        folds=5, lambda_rule="min", clip=0.01,
-                       method="DML-IRM policy tree (LASSO)", run=None) -> PolicyTreeResult:
+                       method="DML-IRM policy tree (LASSO)", run=None,
+                       propensity="linear") -> PolicyTreeResult:
     """Whom to treat: the exact policy tree of depth <= 2 on the AIPW scores of ate_dml_irm
     less ``cost``, over the columns ``features`` of X (1..32) binned into at most ``bins``
     (2..64) bins, every split keeping ``min_leaf`` training rows on each side
@@ -328,7 +348,8 @@ def ate_dml_irm_policy(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.0
     run = _run(run)
     with trace("ate_dml_irm_policy", folds=folds, depth=depth):
         kw = dict(depth=depth, bins=bins, min_leaf=min_leaf, cost=cost, train=train, folds=folds,
-                  seed=run.seed, lambda_rule=lambda_rule, clip=clip, method=method)
+                  seed=run.seed, lambda_rule=lambda_rule, clip=clip, method=method,
+                  propensity=propensity)
         if _ref(run):
             from .reference import estimators as R
             return R.dml_irm_policy_tree(Y, W, X, features, **kw)
@@ -339,13 +360,14 @@ def ate_dml_irm_policy(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.0
 
 def ate_dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0,
                             benchmarks=None, folds=5, lambda_rule="min", clip=0.01,
-                            run=None) -> SensitivityResult:
+                            run=None, propensity="linear") -> SensitivityResult:
     """Sensitivity of ate_dml_irm to unobserved confounding (Chernozhukov, Cinelli, Newey,
     Sharma & Syrgkanis 2022; DoubleML sensitivity_analysis / sensitivity_benchmark): bounds on
     the ATE and their one-sided ``level`` CI under a confounder of strength (cf_y, cf_d,
     rho), the robustness values RV / RVa against ``null``, and the strength of each covariate
     set of ``benchmarks`` (lists of column indices into X, at most 8), from a refit without
     it (estimators/sensitivity.py). Further scenarios: ``result.bounds(cf_y, cf_d, rho)``."""
+    _linear_only(propensity, "ate_dml_irm_sensitivity")
     run = _run(run)
     with trace("ate_dml_irm_sensitivity", folds=folds):
         if _ref(run):
@@ -360,7 +382,8 @@ def ate_dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, 
 
 
 def ate_dml_irm_targets(Y, W, X, targets=("all", "treated", "control"), folds=5,
-                        lambda_rule="min", clip=0.01, run=None, repeats=1) -> TargetResult:
+                        lambda_rule="min", clip=0.01, run=None, repeats=1,
+                        propensity="linear") -> TargetResult:
     """The average effect of ate_dml_irm over other target populations: on the treated
     ("treated", the ATT; DoubleML IRM(score="ATTE"), grf target.sample = "treated") and on
     the controls ("control", the ATC), beside everyone ("all", the ATE of ate_dml_irm), with
@@ -375,15 +398,16 @@ def ate_dml_irm_targets(Y, W, X, targets=("all", "treated", "control"), folds=5,
         if _ref(run):
             from .reference import estimators as R
             return R.dml_irm_targets(Y, W, X, targets, folds=folds, seed=run.seed,
-                                     lambda_rule=lambda_rule, clip=clip, repeats=repeats)
+                                     lambda_rule=lambda_rule, clip=clip, repeats=repeats,
+                                     propensity=propensity)
         from .estimators import targets as DT
         return DT.dml_irm_targets(Y, W, X, targets, folds=folds, seed=run.seed,
                                   lambda_rule=lambda_rule, clip=clip, device=run.device(),
-                                  dtype=run.dtype, repeats=repeats)
+                                  dtype=run.dtype, repeats=repeats, propensity=propensity)
 
 
 def ate_dml_iivm(Y, W, Z, X, folds=5, lambda_rule="min", clip=0.01, always_takers=True,
-                 never_takers=True, run=None) -> LateResult:
+                 never_takers=True, run=None, propensity="linear") -> LateResult:
     """The local average treatment effect (LATE) of the cross-fitted interactive IV model
     (DoubleML DoubleMLIIVM) with CV-LASSO nuisances: the effect of the treatment taken W on
     those whose take-up follows the binary instrument Z (the treatment assigned, e.g. an
@@ -394,6 +418,7 @@ def ate_dml_iivm(Y, W, Z, X, folds=5, lambda_rule="min", clip=0.01, always_taker
     ``subgroups``); that nuisance is then fixed instead of fitted. Repeated cross-fitting,
     group / curve / policy / sensitivity versions and non-binary instruments are not
     available."""
+    _linear_only(propensity, "ate_dml_iivm")
     run = _run(run)
     with trace("ate_dml_iivm", folds=folds):
         if _ref(run):

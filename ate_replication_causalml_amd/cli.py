@@ -44,7 +44,14 @@ def _dml(a):
     dev = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
     if a.model == "irm":
         # interactive model: arm-split panel (segment 2k + a = fold k, W = a), AIPW score
-        from .estimators.irm import irm_crossfit_panel
+        from .estimators.irm import check_logit_scope, irm_crossfit_panel
+        pk = {} if a.propensity == "linear" else {"propensity": a.propensity}
+        try:
+            check_logit_scope(a.propensity, a.p, a.folds, a.dtype, repeats=a.repeats)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if pk and a.sensitivity:
+            raise SystemExit("--propensity logit is not available with --sensitivity")
         if a.repeats > 1:
             # repeated cross-fitting: 2 K*K micro-arm segments, `repeats` K-fold partitions
             if (a.gate_col is not None or a.cate_col is not None or a.policy_cols is not None
@@ -80,11 +87,12 @@ def _dml(a):
             except ValueError as e:
                 raise SystemExit(str(e))
             tg = tuple(t for t in TARGETS if t in tg)
-            mom, _ = irm_targets_panel(pan, a.folds, tg, a.lambda_rule, a.clip)
+            mom, _ = irm_targets_panel(pan, a.folds, tg, a.lambda_rule, a.clip, **pk)
             v = mom.double().cpu().numpy()
             r = TargetResult.from_moments("DML-IRM target populations (LASSO)", v, tg, n=a.n)
             out = {"targets": list(r.targets), "estimates": r.rows(), "cov": r.cov,
-                   "n_treated": int(round(float(v[11]))), "n_clipped": int(round(float(v[3])))}
+                   "n_treated": int(round(float(v[11]))), "n_clipped": int(round(float(v[3]))),
+                   **pk}
             if "treated" in tg and "control" in tg:
                 from dataclasses import asdict
                 out["contrast"] = asdict(r.contrast("treated", "control"))
@@ -120,14 +128,15 @@ def _dml(a):
             use = torch.where(real, 0, -1).to(torch.int8)
             fin, rec, e, _ = DP.irm_policy_panel(pan, codes, use, [len(ed) + 1 for ed in edges],
                                                  a.policy_cost, a.folds, a.policy_depth, 1,
-                                                 a.lambda_rule, a.clip, n_rows=a.n)
+                                                 a.lambda_rule, a.clip, n_rows=a.n, **pk)
             r = PolicyTreeResult.make("DML-IRM policy tree (LASSO)", rec.cpu().numpy(),
                                       fin.double().cpu().numpy(), cols, edges, a.policy_cost,
                                       a.policy_depth, e=int(e.item()))
             ev = r.in_sample
             out = {"nodes": r.nodes, "actions": r.actions, "leaves": ev["leaves"],
                    **{k: v for k, v in ev.items() if k != "leaves"}, "honest": False,
-                   "depth": r.depth, "cost": r.cost, "features": r.features, "edges": r.edges}
+                   "depth": r.depth, "cost": r.cost, "features": r.features, "edges": r.edges,
+                   **pk}
             print(json.dumps(out))
             return 0
         if a.cate_col is not None:
@@ -144,7 +153,8 @@ def _dml(a):
             grid = np.linspace(float(xs[(5 * n) // 100]), float(xs[min((95 * n) // 100, n - 1)]),
                                a.cate_grid)
             fin, _, _, _ = DC.irm_cate_panel(pan, x, knots, a.cate_degree, grid, a.folds,
-                                             a.lambda_rule, a.clip, n_boot=a.boot, seed=a.seed)
+                                             a.lambda_rule, a.clip, n_boot=a.boot, seed=a.seed,
+                                             **pk)
             cate, se, crit, o_ate, o_se, nn, beta, omega = DC.read_fin(
                 fin.double().cpu().numpy(), a.cate_df, a.cate_grid)
             r = CateResult.make("DML-IRM CATE curve (LASSO)", grid, cate, se, crit, beta, omega,
@@ -152,7 +162,7 @@ def _dml(a):
                                 AteResult.make("DML-IRM cross-fit (LASSO)", o_ate, o_se, n=a.n))
             out = {"curve": r.rows(), "crit": r.crit, "n_boot": r.n_boot, "level": r.level,
                    "knots": r.knots, "degree": r.degree, "coef": r.coef, "n": int(round(nn)),
-                   "ate": r.overall.ate, "se": r.overall.se}
+                   "ate": r.overall.ate, "se": r.overall.se, **pk}
             print(json.dumps(out))
             return 0
         if a.gate_col is not None:
@@ -161,7 +171,7 @@ def _dml(a):
             from .result import AteResult, GateResult
             gid, edges = quantile_groups(pan, a.gate_col, a.gate_bins)
             fin, _, _ = irm_gate_panel(pan, gid, a.folds, a.lambda_rule, a.clip, n_boot=a.boot,
-                                       seed=a.seed)
+                                       seed=a.seed, **pk)
             v = fin.double().cpu().numpy()
             G = a.gate_bins
             r = GateResult.make("DML-IRM group ATEs (LASSO)", list(range(G)), v[2 * G:3 * G],
@@ -169,7 +179,8 @@ def _dml(a):
                                 AteResult.make("DML-IRM cross-fit (LASSO)", v[3 * G + 1],
                                                v[3 * G + 2], n=a.n))
             out = {"groups": r.rows(), "crit": r.crit, "n_boot": r.n_boot, "level": r.level,
-                   "edges": edges.cpu().tolist(), "ate": r.overall.ate, "se": r.overall.se}
+                   "edges": edges.cpu().tolist(), "ate": r.overall.ate, "se": r.overall.se,
+                   **pk}
             print(json.dumps(out))
             return 0
         if a.sensitivity:
@@ -193,10 +204,10 @@ def _dml(a):
                    "rv": r.rv, "rva": r.rva, "benchmarks": [asdict(b) for b in r.benchmarks]}
             print(json.dumps(out))
             return 0
-        res, mom, cv = irm_crossfit_panel(pan, a.folds, a.lambda_rule, a.clip)
+        res, mom, cv = irm_crossfit_panel(pan, a.folds, a.lambda_rule, a.clip, **pk)
         r = read_result(res, "DML-IRM cross-fit (LASSO)", n=a.n)
         out = {"ate": r.ate, "se": r.se, "lower_ci": r.lower_ci, "upper_ci": r.upper_ci,
-               "n_clipped": int(round(float(mom[3])))}
+               "n_clipped": int(round(float(mom[3]))), **pk}
     elif a.repeats > 1:
         # repeated cross-fitting: K*K micro-segments, `repeats` distinct K-fold partitions
         pan = synthetic_panel(a.n, p=a.p, folds=a.folds * a.folds, seed=a.seed, dtype=a.dtype,
@@ -277,6 +288,10 @@ def main(argv=None):
                    help="plr: partially linear model; irm: interactive model (cross-fitted AIPW)")
     d.add_argument("--clip", type=float, default=0.01,
                    help="irm: the propensity is clipped to [clip, 1 - clip]")
+    d.add_argument("--propensity", default="linear", choices=["linear", "logit"],
+                   help="irm: the propensity fit -- linear-probability LASSO, or the binomial "
+                        "CV-LASSO (logit: --repeats 1, f32/f64, p <= 96, folds <= 16; not with "
+                        "--sensitivity)")
     d.add_argument("--gate-col", type=int, default=None,
                    help="irm: group ATEs over quantile bins of covariate x{J}, with a joint band")
     d.add_argument("--gate-bins", type=int, default=4, help="irm --gate-col: quantile groups")

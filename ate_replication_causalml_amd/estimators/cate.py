@@ -35,8 +35,8 @@ from ..parallel import rng
 from ..result import AteResult, CateResult
 from .common import as_np
 from .gate import _SLAB_BYTES, boot_crit, check_boot, multiplier_geometry, quantile_groups
-from .irm import (arm_split_panel, comm_counts, irm_finalize, irm_fit_phases, phase_scores,
-                  run_body, run_phases)
+from .irm import (arm_split_panel, check_logit_scope, comm_counts, irm_finalize, irm_fit_phases,
+                  phase_scores, propensity_args, propensity_link, run_body, run_phases)
 
 DF_MAX = 32
 DEGREE_MAX = 3
@@ -295,7 +295,8 @@ def cate_finalize(mom: torch.Tensor, boot: torch.Tensor, beta: torch.Tensor, gba
 
 
 def cate_phases(pan, x, rid, knots, gbasis, degree: int, folds: int, lambda_rule="min",
-                clip=0.01, n_boot=999, level=0.95, seed=1991, comm=None, seg_counts=None):
+                clip=0.01, n_boot=999, level=0.95, seed=1991, comm=None, seg_counts=None,
+                propensity="linear"):
     """The CATE step as phases for utils.graphs.SegmentedStep: those of ``irm_phases`` up to
     the fitted coefficients, then
 
@@ -313,7 +314,8 @@ def cate_phases(pan, x, rid, knots, gbasis, degree: int, folds: int, lambda_rule
     d = knots.numel() - q - 1
     check_basis(d, q)
     check_boot(B, level)
-    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts)
+    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts,
+                                    propensity=propensity)
 
     def phase_moments(st):
         return {**st, "mom": cate_moments(st["psi"], x, rid, knots, q)}
@@ -328,7 +330,7 @@ def cate_phases(pan, x, rid, knots, gbasis, degree: int, folds: int, lambda_rule
         return {**st, "fin": cate_finalize(st["mom"], st["boot"], st["beta"], gbasis, d, q, B,
                                            level)}
 
-    phases += [phase_scores(pan, clip), phase_moments]
+    phases += [phase_scores(pan, clip, propensity_link(propensity)), phase_moments]
     if reduce is not None:
         phases.append(reduce("mom"))
     phases += [phase_beta, phase_boot]
@@ -370,7 +372,7 @@ def check_grid(grid, lo, hi):
 
 def irm_cate_panel(pan, x: torch.Tensor, knots: torch.Tensor, degree: int, grid, folds: int,
                    lambda_rule="min", clip=0.01, n_boot=999, level=0.95, seed=1991, comm=None,
-                   seg_counts=None, rid=None, check=True):
+                   seg_counts=None, rid=None, check=True, propensity="linear"):
     """The CATE curve along ``x`` with a uniform band on an arm-split fold panel (the layout
     of ``irm_crossfit_panel``) -> (fin, mom, boot, cv); ``fin`` as :func:`cate_finalize`.
 
@@ -397,17 +399,17 @@ def irm_cate_panel(pan, x: torch.Tensor, knots: torch.Tensor, degree: int, grid,
         kn = knots.cpu().numpy()
         gbasis = bspline_basis(check_grid(grid, kn[0], kn[-1]), knots.cpu(), q).to(pan.device)
     st = run_phases(cate_phases(pan, x, rid, knots, gbasis, q, folds, lambda_rule, clip, n_boot,
-                                level, seed, comm, seg_counts))
+                                level, seed, comm, seg_counts, propensity))
     return st["fin"], st["mom"], st["boot"], st.get("cv")
 
 
 def _cate_body(pan, x, rid, knots, gbasis, folds, lambda_rule, clip, degree, n_boot, level, seed,
-               dist=None, counts=None):
+               dist=None, counts=None, propensity="linear"):
     """The whole estimator as one device function (GraphCache captures it): fin | mom | boot."""
     comm, seg_counts = comm_counts(dist, counts)
     fin, mom, boot, _ = irm_cate_panel(pan, x, knots, degree, gbasis, folds, lambda_rule, clip,
                                        n_boot, level, seed, comm=comm, rid=rid, check=False,
-                                       seg_counts=seg_counts)
+                                       seg_counts=seg_counts, propensity=propensity)
     return torch.cat([fin, mom, boot])
 
 
@@ -430,7 +432,7 @@ def read_fin(v, df: int, m: int):
 def dml_irm_cate_lasso(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boot=999, level=0.95,
                        folds=5, seed=1991, lambda_rule="min", clip=0.01,
                        method="DML-IRM CATE curve (LASSO)", device=None, dtype="f64", dist=None,
-                       graph=True, keep_boot=False) -> CateResult:
+                       graph=True, keep_boot=False, propensity="linear") -> CateResult:
     """The conditional average treatment effect of the cross-fitted interactive model
     (``irm.dml_irm_lasso``: same folds, same nuisances, same score) as a B-spline curve along
     one covariate, with pointwise and uniform ``level`` confidence bounds from ``n_boot``
@@ -447,6 +449,7 @@ def dml_irm_cate_lasso(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boo
     inputs, so another column in the same layout replays it. keep_boot: the result's
     ``boot`` holds the raw replicate sums T [n_boot, df], M and the meat."""
     Yn, Xn = as_np(Y), as_np(X)
+    check_logit_scope(propensity, X, folds, dtype, dist)
     check_boot(n_boot, level)
     check_basis(df if knots is None else len(knots) - degree - 1, degree)
     n_boot, q = int(n_boot), int(degree)
@@ -483,7 +486,8 @@ def dml_irm_cate_lasso(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boo
     gbasis = bspline_basis(gr, kn, q).to(pan.device)
     out, g = run_body("dml_irm_cate", _cate_body, (pan, x, rid, knt, gbasis), folds, lambda_rule,
                       float(clip), q, n_boot, float(level), int(seed), dist,
-                      tuple(counts.tolist()), graph=graph, dist=dist)
+                      tuple(counts.tolist()), *propensity_args(propensity), graph=graph,
+                      dist=dist)
     v = out.detach().double().cpu().numpy()
     nf = fin_size(d, m)
     cate, se, crit, o_ate, o_se, n, beta, omega = read_fin(v[:nf], d, m)
@@ -493,6 +497,8 @@ def dml_irm_cate_lasso(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boo
     _, cnt, _, M = split_moments(torch.from_numpy(v[nf:nf + nm]), d, q)
     res = CateResult.make(method, gr, cate, se, crit, beta, omega, kn, q, n_boot, level, overall,
                           hipgraph=g, span_counts=[int(round(c)) for c in cnt.tolist()])
+    if propensity != "linear":
+        res.diagnostics["propensity"] = propensity
     if keep_boot:
         Meat, T = split_boot(torch.from_numpy(v[nf + nm:]), d, n_boot)
         res.boot = {"T": T.numpy().copy(), "M": M.numpy().copy(), "meat": Meat.numpy().copy()}

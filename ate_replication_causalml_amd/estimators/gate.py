@@ -30,7 +30,8 @@ from ..parallel import rng
 from ..result import AteResult, GateResult, boot_rank
 from .common import as_np
 from .irm import (arm_split_panel, comm_counts, irm_finalize, irm_fit_phases, mean_se,
-                  phase_scores, run_body, run_phases)
+                  phase_scores, propensity_args, propensity_link, check_logit_scope, run_body,
+                  run_phases)
 
 N_GROUPS_MAX = 64
 N_BOOT_MAX = 4096
@@ -176,7 +177,8 @@ def quantile_groups(pan, col, bins: int, edges: torch.Tensor | None = None):
 
 
 def gate_phases(pan, gid, rid, n_groups: int, folds: int, lambda_rule="min", clip=0.01,
-                n_boot=999, level=0.95, seed=1991, comm=None, seg_counts=None):
+                n_boot=999, level=0.95, seed=1991, comm=None, seg_counts=None,
+                propensity="linear"):
     """The group-effect step as phases for utils.graphs.SegmentedStep: those of
     ``irm_phases`` up to the fitted coefficients, then
 
@@ -189,7 +191,8 @@ def gate_phases(pan, gid, rid, n_groups: int, folds: int, lambda_rule="min", cli
     "coef" and "cv"."""
     G, B = int(n_groups), int(n_boot)
     check_boot(B, level)
-    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts)
+    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts,
+                                    propensity=propensity)
 
     def phase_boot(st):
         return {**st, "boot": group_boot(st["psi"], gid, rid, G, B, seed)}
@@ -197,7 +200,7 @@ def gate_phases(pan, gid, rid, n_groups: int, folds: int, lambda_rule="min", cli
     def phase_final(st):
         return {**st, "fin": gate_finalize(st["boot"], G, B, level)}
 
-    phases += [phase_scores(pan, clip), phase_boot]
+    phases += [phase_scores(pan, clip, propensity_link(propensity)), phase_boot]
     if reduce is not None:
         phases.append(reduce("boot"))
     phases.append(phase_final)
@@ -213,7 +216,8 @@ def group_counts(gid: torch.Tensor, n_groups: int, comm=None) -> np.ndarray:
 
 
 def irm_gate_panel(pan, gid: torch.Tensor, folds: int, lambda_rule="min", clip=0.01, n_boot=999,
-                   level=0.95, seed=1991, comm=None, seg_counts=None, rid=None, n_groups=None):
+                   level=0.95, seed=1991, comm=None, seg_counts=None, rid=None, n_groups=None,
+                   propensity="linear"):
     """Group ATEs with a joint band on an arm-split fold panel (the layout of
     ``irm_crossfit_panel``) -> (fin [3 G + 3], boot buffer, cv).
 
@@ -237,22 +241,24 @@ def irm_gate_panel(pan, gid: torch.Tensor, folds: int, lambda_rule="min", clip=0
     if rid is None:
         rid = pan.row_index
     st = run_phases(gate_phases(pan, gid, rid, n_groups, folds, lambda_rule, clip, n_boot, level,
-                                seed, comm, seg_counts))
+                                seed, comm, seg_counts, propensity))
     return st["fin"], st["boot"], st.get("cv")
 
 
 def _gate_body(pan, gid, rid, folds, lambda_rule, clip, n_groups, n_boot, level, seed, dist=None,
-               counts=None):
+               counts=None, propensity="linear"):
     """The whole estimator as one device function (GraphCache captures it): fin | boot."""
     comm, seg_counts = comm_counts(dist, counts)
     fin, boot, _ = irm_gate_panel(pan, gid, folds, lambda_rule, clip, n_boot, level, seed,
-                                  comm=comm, rid=rid, n_groups=n_groups, seg_counts=seg_counts)
+                                  comm=comm, rid=rid, n_groups=n_groups, seg_counts=seg_counts,
+                                  propensity=propensity)
     return torch.cat([fin, boot])
 
 
 def dml_irm_gate_lasso(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", clip=0.01,
                        n_boot=999, level=0.95, method="DML-IRM group ATEs (LASSO)", device=None,
-                       dtype="f64", dist=None, graph=True, keep_boot=False) -> GateResult:
+                       dtype="f64", dist=None, graph=True, keep_boot=False,
+                       propensity="linear") -> GateResult:
     """Group average treatment effects of the cross-fitted interactive model
     (``irm.dml_irm_lasso``: same folds, same nuisances, same score) with pointwise and
     simultaneous ``level`` confidence bounds from ``n_boot`` Rademacher multiplier draws.
@@ -261,7 +267,9 @@ def dml_irm_gate_lasso(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", c
 
     graph: as ``dml_irm_lasso``, one captured hipGraph on a GPU; the group codes are a graph
     input, so a call with other groups in the same panel layout replays it. keep_boot: the
-    result's ``boot`` holds the raw replicate sums A, Z [n_boot, G]."""
+    result's ``boot`` holds the raw replicate sums A, Z [n_boot, G]. propensity: as
+    ``dml_irm_lasso`` ("logit": the binomial CV-LASSO propensity, with its limits)."""
+    check_logit_scope(propensity, X, folds, dtype, dist)
     check_boot(n_boot, level)
     n_boot = int(n_boot)
     gl = np.asarray(groups)
@@ -286,13 +294,16 @@ def dml_irm_gate_lasso(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", c
                       torch.full((pan.ld,), -1, dtype=torch.int32, device=pan.device))
     out, g = run_body("dml_irm_gate", _gate_body, (pan, gid, rid), folds, lambda_rule,
                       float(clip), G, n_boot, float(level), int(seed), dist,
-                      tuple(counts.tolist()), graph=graph, dist=dist)
+                      tuple(counts.tolist()), *propensity_args(propensity), graph=graph,
+                      dist=dist)
     v = out.detach().double().cpu().numpy()
     theta, se, n = v[:G], v[G:2 * G], v[2 * G:3 * G]
     crit, o_ate, o_se = v[3 * G:3 * G + 3]
     overall = AteResult.make("DML-IRM cross-fit (LASSO)", o_ate, o_se,
                              n=int(round(n.sum())) if np.isfinite(n).all() else -1)
     res = GateResult.make(method, labels, n, theta, se, crit, n_boot, level, overall, hipgraph=g)
+    if propensity != "linear":
+        res.diagnostics["propensity"] = propensity
     if keep_boot:
         _, A, Z = split_boot(torch.from_numpy(v[3 * G + 3:]), G, n_boot)
         res.boot = {"A": A.numpy().copy(), "Z": Z.numpy().copy()}

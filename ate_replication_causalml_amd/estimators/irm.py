@@ -10,6 +10,12 @@ m(X) = E[W|X], all by gaussian CV-LASSO, and averages the doubly robust score
 
 over held-out rows (textbook signs, as ``crossfit.aipw_score``).
 
+``propensity="logit"`` replaces the linear-probability fit of m by the binomial CV-LASSO
+(``cv.glmnet(family="binomial")`` on the same training rows and inner folds): g0 and g1 stay in
+the gaussian launch, all K * K propensity problems run in ONE grouped binomial path launch
+(``ops/lognet.cv_lognet_groups``), and the score pass takes the logit through a logistic link
+(:func:`irm_fit_phases`, :func:`check_logit_scope` for its limits).
+
 Layout: a 2K-segment panel, segment ``2k + a`` = the rows of fold k with W = a. One Gram
 pass (K01) then yields per-(fold, arm) Grams; the fold Grams of the propensity problems are
 their pairwise sums. All 3 K (K + 1) path problems (3 nuisances x K outer folds x (1 full +
@@ -45,6 +51,44 @@ from .common import as_np, resolve_device
 from .lasso import (_fold_ids, _tri_index, allreduce_sym_, global_seg_counts, median_aggregate,
                     micro_fold_map)
 
+PROPENSITIES = ("linear", "logit")   # the fit of m: gaussian LASSO (clipped) | binomial LASSO
+LINKS = ("identity", "logistic")     # what coefficient row 2 predicts: m | logit(m)
+LOGIT_MAX_P, LOGIT_MAX_FOLDS = 96, 16   # ops/lognet: p <= 96, K * K <= 256 path problems
+
+
+def check_propensity(propensity) -> str:
+    if propensity not in PROPENSITIES:
+        raise ValueError(f"propensity must be one of {PROPENSITIES}, got {propensity!r}")
+    return propensity
+
+
+def propensity_link(propensity) -> str:
+    """The link of the score pass for a propensity fit."""
+    return LINKS[PROPENSITIES.index(check_propensity(propensity))]
+
+
+def check_logit_scope(propensity, p, folds, dtype=None, dist=None, repeats=1):
+    """The limits of ``propensity="logit"`` (ValueError naming the one exceeded, before any
+    device work): one partition, no row shards (the binomial path has no collective), an
+    fp32 / fp64 panel, p <= 96 and K <= 16 (K * K path problems in one launch). p: the
+    number of covariates, or the covariate matrix (looked at only for "logit")."""
+    if check_propensity(propensity) == "linear":
+        return
+    p = int(p) if np.ndim(p) == 0 else np.shape(p)[1]       # p, or the covariate matrix
+    if repeats != 1:
+        raise ValueError('propensity="logit" supports repeats = 1 only (no repeated '
+                         "cross-fitting of the binomial path)")
+    if dist is not None:
+        raise ValueError('propensity="logit" does not support row-sharded calls (dist): the '
+                         "binomial path has no collective")
+    if dtype in ("bf16", torch.bfloat16):
+        raise ValueError('propensity="logit" needs an fp32 / fp64 panel, not bf16')
+    if p > LOGIT_MAX_P:
+        raise ValueError(f'propensity="logit" supports p <= {LOGIT_MAX_P} covariates, got {p}')
+    if folds > LOGIT_MAX_FOLDS:
+        raise ValueError(f'propensity="logit" supports K <= {LOGIT_MAX_FOLDS} folds, got {folds}')
+
+
 N_MOMENTS = 8   # [S psi, S psi^2, n, n_clipped, S w(y-g1)^2, S (1-w)(y-g0)^2, S (w-m)^2, n_treated]
 
 
@@ -69,14 +113,16 @@ def _score_args(pan, coef, segs_per_fold):
     return p
 
 
-def _score_terms(pan, coef, segs_per_fold, blk=None):
+def _score_terms(pan, coef, segs_per_fold, blk=None, link="identity"):
     """The float64 CPU twin of the score pass (the kernels' oracle): per segment
     ``(r0, r1, v, y, w, g0, g1, m)`` -- its row range, the mask of its real rows, and over
-    those rows the targets, the two outcome regressions and the unclipped propensity.
+    those rows the targets, the two outcome regressions and the unclipped propensity
+    (link "logistic": coefficient row 2 predicts its logit, m = 1 / (1 + exp(-eta))).
     blk [S, ngroups] (the multi-split pass): segment group g uses block ``blk[t][g]`` under
     split t, and g0, g1, m are lists of S tensors, each the expression of the single pass."""
     if blk is None:
         _score_args(pan, coef, segs_per_fold)
+    logistic = _link_code(link, pan) == 1
     y0, y1, w0, w1 = _yw_columns(pan)
     X = pan.colmajor().double()
     c = coef.double()
@@ -93,8 +139,23 @@ def _score_terms(pan, coef, segs_per_fold, blk=None):
             yield (r0, r1, v, y, w, *([c[q, r, 0] + c[q, r, 1:] @ xs for q in ks]
                                       for r in range(3)))
             continue
-        yield (r0, r1, v, y, w, c[k, 0, 0] + c[k, 0, 1:] @ xs, c[k, 1, 0] + c[k, 1, 1:] @ xs,
-               c[k, 2, 0] + c[k, 2, 1:] @ xs)
+        m = c[k, 2, 0] + c[k, 2, 1:] @ xs
+        if logistic:
+            m = 1.0 / (1.0 + torch.exp(-m))
+        yield (r0, r1, v, y, w, c[k, 0, 0] + c[k, 0, 1:] @ xs, c[k, 1, 0] + c[k, 1, 1:] @ xs, m)
+
+
+def _link_code(link, pan) -> int:
+    """0 identity, 1 logistic; the logistic link exists for fp32 / fp64 panels only."""
+    if link not in LINKS:
+        raise ValueError(f"link must be one of {LINKS}, got {link!r}")
+    if link == "logistic" and pan.dtype == torch.bfloat16:
+        raise ValueError("the logistic link of the score pass needs an fp32 / fp64 panel")
+    return LINKS.index(link)
+
+
+_LINK_MODES = {"ate_irm_score_moments": 0, "ate_irm_scores": 1, "ate_irm_sens_moments": 2,
+               "ate_irm_target_moments": 3}
 
 
 def aipw_psi(y, w, g0, g1, e):
@@ -102,12 +163,19 @@ def aipw_psi(y, w, g0, g1, e):
     return g1 - g0 + w * (y - g1) / e - (1.0 - w) * (y - g0) / (1.0 - e)
 
 
-def _score_launch(name, pan, coef, clip, segs_per_fold, nbx, n_out, moments, blk=None):
+def _score_launch(name, pan, coef, clip, segs_per_fold, nbx, n_out, moments, blk=None,
+                  link="identity"):
     """One instantiation of the fused score pass (csrc/irm.hip entry point ``name``) with
     ``nbx`` blocks per segment. ``moments``: the entry point sums ``n_out`` moments (a
     ``partial`` workspace, then the result); otherwise it writes ``n_out`` = ld row scores.
     blk [S, ngroups] (checked by the caller): the multi-split entry point, whose arguments
-    add (nblk, blk, S) after ``coef``; ``n_out`` = S * 8 then."""
+    add (nblk, blk, S) after ``coef``; ``n_out`` = S * 8 then. link "logistic": the same pass
+    through ``ate_irm_score_link`` (mode of ``name``, link 1); "identity" keeps ``name``."""
+    head = ()
+    if _link_code(link, pan):
+        if blk is not None:
+            raise ValueError("the multi-split score pass has no logistic link")
+        head, name = (_LINK_MODES[name], 1), "ate_irm_score_link"
     p = len(pan.xcols) if blk is not None else _score_args(pan, coef, segs_per_fold)
     y0, y1, w0, w1 = _yw_columns(pan)
     dev = pan.device
@@ -124,26 +192,32 @@ def _score_launch(name, pan, coef, clip, segs_per_fold, nbx, n_out, moments, blk
     split = () if blk is None else (coef.shape[0], const(blk, torch.int32, dev).data_ptr(),
                                     blk.shape[0])
     cs, bs = pan.strides()
-    _native.call(name, dtype_code(pan.data), pan.data.data_ptr(), cs, bs, xc.data_ptr(), p,
+    ptrs = [b.data_ptr() for b in bufs]
+    if head and not moments:
+        ptrs.append(None)                        # the link entry point's unused `moments`
+    _native.call(name, *head, dtype_code(pan.data), pan.data.data_ptr(), cs, bs, xc.data_ptr(), p,
                  segs.data_ptr(), pan.nseg, segs_per_fold, c.data_ptr(), *split, y0, y1, w0, w1,
-                 pan.cols["one"], float(clip), nbx, *(b.data_ptr() for b in bufs),
+                 pan.cols["one"], float(clip), nbx, *ptrs,
                  torch.cuda.current_stream().cuda_stream)
     return out
 
 
 def irm_score_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
-                      nbx: int | None = None) -> torch.Tensor:
+                      nbx: int | None = None, link: str = "identity") -> torch.Tensor:
     """Fused held-out AIPW score pass -> the 8 fp64 moments (N_MOMENTS).
 
     coef: [nfold, 3, p+1] fp64, rows (g0, g1, m), intercept first; segment s of the panel
     uses block ``s // segs_per_fold`` (2: the arm-split layout; 1: a plain K-fold panel).
     W is read from the panel on every row. GPU: csrc/irm.hip (``nbx`` blocks per segment);
-    CPU: the float64 torch twin (:func:`_score_terms`), the kernel's oracle."""
+    CPU: the float64 torch twin (:func:`_score_terms`), the kernel's oracle.
+    link "logistic": row m of coef holds logit coefficients (``propensity="logit"``); the
+    sigmoid is taken in fp64 before the score, so n_clipped and S (w - m)^2 are about the
+    probability (fp32 / fp64 panels; the same keyword on the three sibling passes)."""
     if pan.data.is_cuda:
         return _score_launch("ate_irm_score_moments", pan, coef, clip, segs_per_fold, nbx,
-                             N_MOMENTS, True)
+                             N_MOMENTS, True, link=link)
     mom = torch.zeros(N_MOMENTS, dtype=torch.float64)
-    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
+    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold, link=link):
         mom += _segment_moments(y, w, g0, g1, m, clip)
     return mom
 
@@ -199,7 +273,7 @@ def irm_score_moments_multi(pan, coef: torch.Tensor, blk, clip: float = 0.01,
 
 
 def irm_sens_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
-                     nbx: int | None = None) -> torch.Tensor:
+                     nbx: int | None = None, link: str = "identity") -> torch.Tensor:
     """The pass of :func:`irm_score_moments` -- same arguments, same dot products, same psi --
     accumulating the 14 fp64 moments of the sensitivity analysis (``result.SENS_MOMENTS``;
     estimators/sensitivity.py). GPU: csrc/irm.hip ``ate_irm_sens_moments`` (for the same
@@ -207,10 +281,10 @@ def irm_sens_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold:
     ``irm_score_moments``); CPU: the float64 torch twin."""
     if pan.data.is_cuda:
         return _score_launch("ate_irm_sens_moments", pan, coef, clip, segs_per_fold, nbx,
-                             len(SENS_MOMENTS), True)
+                             len(SENS_MOMENTS), True, link=link)
     mom = torch.zeros(len(SENS_MOMENTS), dtype=torch.float64)
     lo, hi = clip, 1.0 - clip
-    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
+    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold, link=link):
         e = m.clamp(lo, hi)
         psi = aipw_psi(y, w, g0, g1, e)
         b = torch.where(w != 0, (y - g1) ** 2, (y - g0) ** 2)
@@ -226,7 +300,7 @@ def irm_sens_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold:
 
 
 def irm_target_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
-                       nbx: int | None = None) -> torch.Tensor:
+                       nbx: int | None = None, link: str = "identity") -> torch.Tensor:
     """The pass of :func:`irm_score_moments` -- same arguments, same dot products, same psi --
     accumulating the 12 fp64 moments of the three target populations (``result.TARGET_MOMENTS``;
     estimators/targets.py): with e the clipped propensity and the two quotients of psi,
@@ -241,10 +315,10 @@ def irm_target_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fol
     that was not fitted) is legal: the moments that involve it are finite and meaningless."""
     if pan.data.is_cuda:
         return _score_launch("ate_irm_target_moments", pan, coef, clip, segs_per_fold, nbx,
-                             len(TARGET_MOMENTS), True)
+                             len(TARGET_MOMENTS), True, link=link)
     mom = torch.zeros(len(TARGET_MOMENTS), dtype=torch.float64)
     lo, hi = clip, 1.0 - clip
-    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
+    for _, _, _, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold, link=link):
         e = m.clamp(lo, hi)
         psi = aipw_psi(y, w, g0, g1, e)
         q1, q0 = w * (y - g1) / e, (1.0 - w) * (y - g0) / (1.0 - e)
@@ -260,7 +334,7 @@ def irm_target_moments(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fol
 
 
 def irm_scores(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int = 2,
-               nbx: int | None = None) -> torch.Tensor:
+               nbx: int | None = None, link: str = "identity") -> torch.Tensor:
     """The per-row AIPW scores psi [ld] (fp64, panel row order, 0 on padding rows): the pass
     of :func:`irm_score_moments` -- same arguments, same dot products, same psi -- writing
     every row's score instead of summing moments (csrc/irm.hip ``ate_irm_scores``; CPU: the
@@ -269,9 +343,10 @@ def irm_scores(pan, coef: torch.Tensor, clip: float = 0.01, segs_per_fold: int =
         bounds = np.asarray(pan.seg_bounds, dtype=np.int64)
         if bounds[0, 0] != 0 or bounds[-1, 1] != pan.ld or np.any(bounds[1:, 0] != bounds[:-1, 1]):
             raise ValueError("the panel's segments must tile [0, ld): every row gets a score")
-        return _score_launch("ate_irm_scores", pan, coef, clip, segs_per_fold, nbx, pan.ld, False)
+        return _score_launch("ate_irm_scores", pan, coef, clip, segs_per_fold, nbx, pan.ld, False,
+                             link=link)
     psi = torch.zeros(pan.ld, dtype=torch.float64)
-    for r0, r1, v, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold):
+    for r0, r1, v, y, w, g0, g1, m in _score_terms(pan, coef, segs_per_fold, link=link):
         psi[r0:r1][v] = aipw_psi(y, w, g0, g1, m.clamp(clip, 1.0 - clip))
     return psi
 
@@ -299,7 +374,8 @@ def check_cells(counts, folds: int):
                          "has no rows")
 
 
-def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_counts=None):
+def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_counts=None,
+               propensity="linear"):
     """The cross-fit DML-IRM step as phases for utils.graphs.SegmentedStep (as
     lasso.dml_phases):
 
@@ -312,11 +388,14 @@ def irm_phases(pan, folds: int, lambda_rule="min", clip=0.01, comm=None, seg_cou
     C  theta / SE (fp64, on device)                                      device
 
     Every rank solves every path (paths are not sharded over ranks). The result state holds
-    "res" [2], "mom" [8], "coef" [K, 3, p+1] and "cv"."""
-    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts)
+    "res" [2], "mom" [8], "coef" [K, 3, p+1] and "cv". propensity "logit": m by the grouped
+    binomial path (:func:`irm_fit_phases`), scored through the logistic link."""
+    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts,
+                                    propensity=propensity)
+    link = propensity_link(propensity)
 
     def phase_score(st):
-        return {**st, "mom": irm_score_moments(pan, st["coef"], clip, 2)}
+        return {**st, "mom": irm_score_moments(pan, st["coef"], clip, 2, link=link)}
 
     def phase_final(st):
         return {**st, "res": irm_finalize(st["mom"])}
@@ -392,8 +471,15 @@ def gram_phases(pan, comm=None):
     return phases, (reduce if dist else None)
 
 
+def logit_fold_sets(K: int):
+    """The K cross-validated binomial fits of the logit propensity as ``full_sets`` of
+    ``ops.lognet.cv_lognet_groups``: group k trains on every fold but k, its CV folds are the
+    other folds in ascending order, fold j = the two arm segments (2j, 2j + 1)."""
+    return [[(2 * j, 2 * j + 1) for j in range(K) if j != k] for k in range(K)]
+
+
 def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None,
-                   nuisances=NUISANCES):
+                   nuisances=NUISANCES, propensity="linear"):
     """The phases of :func:`irm_phases` up to the fitted coefficients (A, C01, B; state "G",
     "cv", "coef"), shared with the group-effect estimator (estimators/gate.py), and the
     factory ``reduce(name)`` of an all-reduce phase of a state tensor (None at world 1).
@@ -404,9 +490,18 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
     coefficients are scattered into "coef" [K, 3, p+1], whose other rows are zero. The launch
     keeps the lambda ratio of the whole fit (``default_lambda_min_ratio`` over the training
     sets of all three nuisances), so a nuisance does not depend on which others are fitted
-    beside it. The default fits all three with today's call."""
+    beside it. The default fits all three with today's call.
+
+    propensity "logit": the gaussian launch names only the requested ones of g0 and g1 (the
+    subset path above: their coefficients carry the bits of the linear fit), and ONE grouped
+    binomial launch (``ops.lognet.cv_lognet_groups``: the K outer training sets, then their
+    K (K - 1) inner folds) fits m; row 2 of "coef" then holds logit coefficients, for the
+    logistic link of the score pass. State "cv_m": the binomial fit. Limits:
+    :func:`check_logit_scope`."""
     dist = comm is not None and comm.world_size > 1
     K = folds
+    logit = check_propensity(propensity) == "logit"
+    check_logit_scope(propensity, len(pan.xcols), K, pan.dtype, comm)
     if seg_counts is None:
         seg_counts = global_seg_counts(pan, comm) if dist else np.asarray(pan.seg_nreal)
     counts = np.asarray(seg_counts, dtype=np.float64)
@@ -414,6 +509,12 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
     if pan.nseg != 2 * K:
         raise ValueError(f"DML-IRM needs {2 * K} segments, this shard's panel has {pan.nseg}")
     nuisances = check_nuisances(nuisances)
+    fit_m = logit and 2 in nuisances
+    if logit:
+        nuisances = tuple(r for r in nuisances if r != 2)
+    if not nuisances:
+        raise ValueError('propensity="logit" needs an outcome regression (g0 or g1) among the '
+                         "nuisances")
     counts3, full_sets, full_y, ycols = fit_problems(pan, K, counts, nuisances)
     subset = nuisances != NUISANCES
     ratio = None
@@ -433,6 +534,11 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
             some = coef.reshape(K, len(nuisances), -1).double()
             coef = torch.zeros(K, 3, some.shape[2], dtype=torch.float64, device=some.device)
             coef.index_copy_(1, slots, some)
+            if fit_m:
+                from ..ops.lognet import cv_lognet_groups
+                cvm = cv_lognet_groups(pan, pan.xcols, pan.cols["W"], logit_fold_sets(K))
+                coef[:, 2] = cvm.coef_min if lambda_rule == "min" else cvm.coef_1se
+                return {**st, "cv": cv, "cv_m": cvm, "coef": coef}
             return {**st, "cv": cv, "coef": coef}
         return {**st, "cv": cv, "coef": coef.reshape(K, 3, -1).double().contiguous()}
 
@@ -441,11 +547,12 @@ def irm_fit_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=Non
     return phases, reduce
 
 
-def phase_scores(pan, clip):
+def phase_scores(pan, clip, link="identity"):
     """The phase after :func:`irm_fit_phases` of every estimator on the per-row scores:
-    state "psi" [ld] (csrc/irm.hip ``ate_irm_scores``)."""
+    state "psi" [ld] (csrc/irm.hip ``ate_irm_scores``; link: that of the propensity fit,
+    :func:`propensity_link`)."""
     def f(st):
-        return {**st, "psi": irm_scores(pan, st["coef"], clip, 2)}
+        return {**st, "psi": irm_scores(pan, st["coef"], clip, 2, link=link)}
     return f
 
 
@@ -458,7 +565,7 @@ def run_phases(phases) -> dict:
 
 
 def irm_crossfit_panel(pan, folds: int, lambda_rule="min", clip=0.01, comm=None,
-                       seg_counts=None):
+                       seg_counts=None, propensity="linear"):
     """DML-IRM on an arm-split fold panel (segment 2k + a = fold k, W = a; from host arrays
     ``build_panel(X, W, Y, folds=2 * fold + W)``, at scale
     ``data.device_dgp.synthetic_panel(arm_split=True)``). Returns (res[2], mom[8], cv).
@@ -467,7 +574,7 @@ def irm_crossfit_panel(pan, folds: int, lambda_rule="min", clip=0.01, comm=None,
     segment; the Gram stack and the score moments are all-reduced. seg_counts: global rows
     per segment (one all-reduce when omitted). A truncated CV fold path NaN-poisons the
     picked coefficients (ops/enet), and through them res."""
-    st = run_phases(irm_phases(pan, folds, lambda_rule, clip, comm, seg_counts))
+    st = run_phases(irm_phases(pan, folds, lambda_rule, clip, comm, seg_counts, propensity))
     return st["res"], st["mom"], st.get("cv")
 
 
@@ -661,17 +768,23 @@ def run_body(name, body, tensors, *args, graph=True, dist=None):
     return body(*tensors, *args), False
 
 
-def _irm_body(pan, folds, lambda_rule, clip, dist=None, counts=None):
+def propensity_args(propensity) -> tuple:
+    """The trailing static argument of a graph body for the propensity fit: none for the
+    default (its cache key and call stay what they were), the name otherwise."""
+    return () if check_propensity(propensity) == "linear" else (propensity,)
+
+
+def _irm_body(pan, folds, lambda_rule, clip, dist=None, counts=None, propensity="linear"):
     """The whole cross-fit as one device function (GraphCache captures it): [res, mom]."""
     comm, seg_counts = comm_counts(dist, counts)
     res, mom, _ = irm_crossfit_panel(pan, folds, lambda_rule, clip, comm=comm,
-                                     seg_counts=seg_counts)
+                                     seg_counts=seg_counts, propensity=propensity)
     return torch.cat([res, mom])
 
 
 def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
                   method="DML-IRM cross-fit (LASSO)", device=None, dtype="f64", dist=None,
-                  graph=True):
+                  graph=True, propensity="linear"):
     """K-fold cross-fitted AIPW (interactive model) with CV-LASSO nuisances: per-arm
     outcome regressions and the linear-probability propensity, each with an inner CV over
     the other K-1 folds (the fold stream of dml_plr_lasso). W must be exactly {0, 1}.
@@ -680,10 +793,17 @@ def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
     graph: on a GPU (alone, or row-sharded over RCCL) the estimator runs as one captured
     hipGraph (first call of a panel layout eager, captured on the second, replayed after).
     diagnostics: n, n_clipped (propensities outside [clip, 1-clip]), n_treated, the held-out
-    RMSE of the three nuisances, hipgraph."""
+    RMSE of the three nuisances, hipgraph.
+
+    propensity: "linear" (default) or "logit": m by the binomial CV-LASSO
+    (cv.glmnet(family="binomial") on the same training rows and inner folds; all K * K fits
+    in one launch), the score through the logistic link; diagnostics gain ``propensity``.
+    Limits of "logit": one partition, no ``dist``, an fp32 / fp64 panel, p <= 96, K <= 16."""
+    check_logit_scope(propensity, X, folds, dtype, dist)
     pan, counts, _, n, _ = arm_split_panel(Y, W, X, folds, seed, dtype, device, dist)
     out, g = run_body("dml_irm", _irm_body, (pan,), folds, lambda_rule, float(clip), dist,
-                      tuple(counts.tolist()), graph=graph, dist=dist)
+                      tuple(counts.tolist()), *propensity_args(propensity), graph=graph,
+                      dist=dist)
     v = out.detach().double().cpu().numpy()
     mom = v[2:]
     nt = mom[7]
@@ -692,6 +812,8 @@ def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
                 rmse_g0=float(np.sqrt(mom[5] / (mom[2] - nt))),
                 rmse_g1=float(np.sqrt(mom[4] / nt)), rmse_m=float(np.sqrt(mom[6] / mom[2])),
                 hipgraph=g)
+    if propensity != "linear":
+        diag["propensity"] = propensity
     return AteResult.make(method, v[0], v[1], **diag)
 
 

@@ -36,7 +36,8 @@ from .. import _native
 from ..result import PolicyTreeResult
 from ..utils.graphs import Collective
 from .common import as_np
-from .irm import (arm_split_panel, comm_counts, irm_fit_phases, mean_se, phase_scores, run_body,
+from .irm import (arm_split_panel, check_logit_scope, comm_counts, irm_fit_phases, mean_se,
+                  phase_scores, propensity_args, propensity_link, run_body,
                   run_phases)
 
 N_FEATURES_MAX = 32
@@ -377,7 +378,7 @@ def policy_finalize(sums: torch.Tensor, bad: torch.Tensor) -> torch.Tensor:
 
 # ---------------------------------------------------------------- estimator
 def policy_phases(pan, codes, use, nb, cost, folds: int, depth=2, min_leaf=1, lambda_rule="min",
-                  clip=0.01, comm=None, seg_counts=None, n_rows=None):
+                  clip=0.01, comm=None, seg_counts=None, n_rows=None, propensity="linear"):
     """The policy-tree step as phases for utils.graphs.SegmentedStep: those of ``irm_phases``
     up to the fitted coefficients, then
 
@@ -395,7 +396,8 @@ def policy_phases(pan, codes, use, nb, cost, folds: int, depth=2, min_leaf=1, la
     The result state holds "fin" [2, 20] (:func:`policy_finalize`), "rec" (the tree record),
     "e", "hist", "psi", "coef" and "cv"."""
     check_tree_args(depth, 2, min_leaf)
-    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts)
+    phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts,
+                                    propensity=propensity)
     n_rows = int(n_rows) if n_rows is not None else pan.ld
     cost_t = _dev_scalar(cost, torch.float64, pan.device)
 
@@ -422,7 +424,7 @@ def policy_phases(pan, codes, use, nb, cost, folds: int, depth=2, min_leaf=1, la
             return st
         return Collective(f, capturable=bool(getattr(comm, "capturable", False)))
 
-    phases += [phase_scores(pan, clip), phase_range]
+    phases += [phase_scores(pan, clip, propensity_link(propensity)), phase_range]
     if reduce is not None:
         phases.append(reduce_max("range"))
     phases.append(phase_hist)
@@ -437,7 +439,7 @@ def policy_phases(pan, codes, use, nb, cost, folds: int, depth=2, min_leaf=1, la
 
 def irm_policy_panel(pan, codes: torch.Tensor, use: torch.Tensor, nb, cost=0.0, folds: int = 5,
                      depth=2, min_leaf=1, lambda_rule="min", clip=0.01, comm=None,
-                     seg_counts=None, n_rows=None):
+                     seg_counts=None, n_rows=None, propensity="linear"):
     """The policy tree on an arm-split fold panel (the layout of ``irm_crossfit_panel``) ->
     (fin [2, 20], rec int64 [16], e int32 [1], cv). When a score of a row in use is not finite
     every entry of fin is NaN and rec is the bare root leaf that treats nobody
@@ -452,25 +454,25 @@ def irm_policy_panel(pan, codes: torch.Tensor, use: torch.Tensor, nb, cost=0.0, 
         raise ValueError(f"codes must be [d, {pan.ld}] and use [{pan.ld}], got "
                          f"{tuple(codes.shape)} and {tuple(use.shape)}")
     st = run_phases(policy_phases(pan, codes, use, nb, cost, folds, depth, min_leaf, lambda_rule,
-                                  clip, comm, seg_counts, n_rows))
+                                  clip, comm, seg_counts, n_rows, propensity))
     return st["fin"], st["rec"], st["e"], st.get("cv")
 
 
 def _policy_body(pan, codes, use, nb, cost, folds, lambda_rule, clip, depth, min_leaf, n_rows,
-                 dist=None, counts=None):
+                 dist=None, counts=None, propensity="linear"):
     """The whole estimator as one device function (GraphCache captures it):
     (fin [2, 20] fp64, rec | e int64 [17])."""
     comm, seg_counts = comm_counts(dist, counts)
     fin, rec, e, _ = irm_policy_panel(pan, codes, use, nb, cost, folds, depth, min_leaf,
                                       lambda_rule, clip, comm=comm, n_rows=n_rows,
-                                      seg_counts=seg_counts)
+                                      seg_counts=seg_counts, propensity=propensity)
     return fin, torch.cat([rec, e.to(torch.int64)])
 
 
 def dml_irm_policy_lasso(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.0, train=None,
                          folds=5, seed=1991, lambda_rule="min", clip=0.01,
                          method="DML-IRM policy tree (LASSO)", device=None, dtype="f64", dist=None,
-                         graph=True) -> PolicyTreeResult:
+                         graph=True, propensity="linear") -> PolicyTreeResult:
     """Whom to treat: the exact depth <= 2 policy tree on the AIPW scores of the cross-fitted
     interactive model (``irm.dml_irm_lasso``: same folds, same nuisances, same score), over
     the columns ``features`` of X (1..32 distinct indices) binned into at most ``bins`` (2..64)
@@ -489,6 +491,7 @@ def dml_irm_policy_lasso(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0
     bin counts and the cost are graph inputs, so a call with other features (as many) and
     another cost in the same panel layout replays it."""
     Xn = as_np(X)
+    check_logit_scope(propensity, X, folds, dtype, dist)
     check_tree_args(depth, bins, min_leaf)
     feats = check_features(features, Xn.shape[1])
     if not np.isfinite(float(cost)):
@@ -524,9 +527,11 @@ def dml_irm_policy_lasso(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0
     cost_t = torch.tensor([float(cost)], dtype=torch.float64, device=pan.device)
     out, g = run_body("dml_irm_policy", _policy_body, (pan, codes, use, nbt, cost_t), folds,
                       lambda_rule, float(clip), int(depth), int(min_leaf), int(n_total), dist,
-                      tuple(counts.tolist()), graph=graph, dist=dist)
+                      tuple(counts.tolist()), *propensity_args(propensity), graph=graph,
+                      dist=dist)
     fin = out[0].detach().double().cpu().numpy()
     rec = out[1].detach().cpu().numpy().astype(np.int64)
+    extra = {} if propensity == "linear" else {"propensity": propensity}
     return PolicyTreeResult.make(method, rec[:REC], fin, feats, edges, float(cost), int(depth),
                                  held_out=train is not None, hipgraph=g, e=int(rec[REC]),
-                                 min_leaf=int(min_leaf), bins=int(bins))
+                                 min_leaf=int(min_leaf), bins=int(bins), **extra)

@@ -40,7 +40,8 @@ from __future__ import annotations
 import numpy as np
 
 from ..result import TARGET_MOMENTS, TARGETS, TargetResult, check_targets
-from .irm import (arm_split_panel, comm_counts, irm_fit_phases, irm_target_moments, run_body,
+from .irm import (arm_split_panel, check_logit_scope, comm_counts, irm_fit_phases,
+                  irm_target_moments, propensity_args, propensity_link, run_body,
                   run_phases)
 
 N_TARGET = len(TARGET_MOMENTS)   # 12
@@ -54,7 +55,7 @@ def target_nuisances(targets) -> tuple:
 
 
 def target_phases(pan, folds: int, targets=TARGETS, lambda_rule="min", clip=0.01, comm=None,
-                  seg_counts=None):
+                  seg_counts=None, propensity="linear"):
     """The target step as phases for utils.graphs.SegmentedStep: those of ``irm_phases`` up
     to the fitted coefficients, with only the nuisances ``targets`` need in the path launch
     (``irm_fit_phases(nuisances=)``), then
@@ -65,10 +66,11 @@ def target_phases(pan, folds: int, targets=TARGETS, lambda_rule="min", clip=0.01
     The result state holds "mom" [12], "coef" [K, 3, p+1] (zero rows for the nuisances that
     were not fitted) and "cv"."""
     phases, reduce = irm_fit_phases(pan, folds, lambda_rule, comm, seg_counts,
-                                    nuisances=target_nuisances(targets))
+                                    nuisances=target_nuisances(targets), propensity=propensity)
+    link = propensity_link(propensity)
 
     def phase_moments(st):
-        return {**st, "mom": irm_target_moments(pan, st["coef"], clip, 2)}
+        return {**st, "mom": irm_target_moments(pan, st["coef"], clip, 2, link=link)}
 
     phases.append(phase_moments)
     if reduce is not None:
@@ -77,25 +79,27 @@ def target_phases(pan, folds: int, targets=TARGETS, lambda_rule="min", clip=0.01
 
 
 def irm_targets_panel(pan, folds: int, targets=TARGETS, lambda_rule="min", clip=0.01, comm=None,
-                      seg_counts=None):
+                      seg_counts=None, propensity="linear"):
     """The target moments on an arm-split fold panel (the layout of
     ``irm.irm_crossfit_panel``) -> (mom [12], cv). Device tensors, no host sync (capturable);
     ``result.TargetResult.from_moments(method, mom, targets)`` finishes on the host."""
-    st = run_phases(target_phases(pan, folds, targets, lambda_rule, clip, comm, seg_counts))
+    st = run_phases(target_phases(pan, folds, targets, lambda_rule, clip, comm, seg_counts,
+                                  propensity))
     return st["mom"], st.get("cv")
 
 
-def _targets_body(pan, folds, targets, lambda_rule, clip, dist=None, counts=None):
+def _targets_body(pan, folds, targets, lambda_rule, clip, dist=None, counts=None,
+                  propensity="linear"):
     """The whole call as one device function (GraphCache captures it): the 12 moments."""
     comm, seg_counts = comm_counts(dist, counts)
     mom, _ = irm_targets_panel(pan, folds, targets, lambda_rule, clip, comm=comm,
-                               seg_counts=seg_counts)
+                               seg_counts=seg_counts, propensity=propensity)
     return mom
 
 
 def dml_irm_targets(Y, W, X, targets=TARGETS, folds=5, seed=1991, lambda_rule="min", clip=0.01,
                     method="DML-IRM target populations (LASSO)", device=None, dtype="f64",
-                    dist=None, graph=True, repeats=1) -> TargetResult:
+                    dist=None, graph=True, repeats=1, propensity="linear") -> TargetResult:
     """The average effect over everyone ("all"), on the treated ("treated") and on the
     controls ("control") from one cross-fit of ``irm.dml_irm_lasso`` (same folds, same
     nuisances, same score; the "all" row is its theta and SE), with their joint covariance
@@ -110,6 +114,7 @@ def dml_irm_targets(Y, W, X, targets=TARGETS, folds=5, seed=1991, lambda_rule="m
     targets is out of scope (see the module docstring), as are their group, curve and policy
     versions."""
     targets = check_targets(targets)
+    check_logit_scope(propensity, X, folds, dtype, dist, repeats)
     if repeats != 1:
         raise ValueError("repeated cross-fitting is not available for the target populations: "
                          "repeats must be 1")
@@ -117,8 +122,10 @@ def dml_irm_targets(Y, W, X, targets=TARGETS, folds=5, seed=1991, lambda_rule="m
     targets = tuple(t for t in TARGETS if t in targets)
     pan, counts, _, n, _ = arm_split_panel(Y, W, X, folds, seed, dtype, device, dist)
     out, g = run_body("dml_irm_targets", _targets_body, (pan,), folds, targets, lambda_rule,
-                      float(clip), dist, tuple(counts.tolist()), graph=graph, dist=dist)
+                      float(clip), dist, tuple(counts.tolist()), *propensity_args(propensity),
+                      graph=graph, dist=dist)
     mom = out.detach().double().cpu().numpy()
     fin = lambda x: int(round(x)) if np.isfinite(x) else -1
+    extra = {} if propensity == "linear" else {"propensity": propensity}
     return TargetResult.from_moments(method, mom, targets, n=n, n_treated=fin(mom[11]),
-                                     n_clipped=fin(mom[3]), hipgraph=g)
+                                     n_clipped=fin(mom[3]), hipgraph=g, **extra)

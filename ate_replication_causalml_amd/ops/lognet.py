@@ -5,6 +5,10 @@ segments but k, on the full problem's lambda sequence), evaluates held-out binom
 deviance per (fold, lambda), and applies the cv.glmnet selection rules
 (``ate_cv_select``, shared with the gaussian path). Three launches + selection, no
 host synchronisation. CPU tensors run reference/glmnet.py on the same folds.
+
+``cv_lognet_groups`` runs several such cross-validated fits -- the K outer training sets of a
+cross-fit with their inner folds, a fold being any set of segments -- in ONE path launch
+(``ate_lognet_path_groups``), one held-out deviance launch over segment sets and one selection.
 """
 from __future__ import annotations
 
@@ -15,7 +19,12 @@ import torch
 
 from .. import _native
 from ..reference import glmnet as ref
+from .devconst import const
 from .panel import dtype_code
+
+MAX_PATH_PROBLEMS = 256   # co-resident workgroups of one concurrent path launch
+MAX_SEGMENTS = 64         # csrc/lognet.hip MAXSEG
+MAX_P = 96
 
 
 @dataclass
@@ -153,3 +162,181 @@ def _cv_cpu(panel, xcols, ycol, vp, alpha, nlambda, flmin, thresh, maxit):
     return LognetCvResult(pad(cv.lambdas), torch.tensor([m], dtype=torch.int32), pad(cv.cvm),
                           pad(cv.cvsd), sel, coef_t, coef_t[cv.idx_min], coef_t[cv.idx_1se],
                           torch.tensor([cv.fit.npasses]))
+
+
+@dataclass
+class LognetGroupsResult:
+    """Per group g (one cross-validated binomial fit): the fields of LognetCvResult stacked."""
+    lambdas: torch.Tensor    # [G, L] (NaN beyond nlam[g])
+    nlam: torch.Tensor       # [G] int32
+    cvm: torch.Tensor        # [G, L]
+    cvsd: torch.Tensor       # [G, L]
+    sel: torch.Tensor        # [G, 2] (idx_min, idx_1se)
+    coef_min: torch.Tensor   # [G, p+1] original scale, intercept first
+    coef_1se: torch.Tensor   # [G, p+1]
+    npass: torch.Tensor      # [nprob]: the G full fits, then every group's fold fits (< 0:
+                             # the wait for the group's full fit timed out)
+
+    def check(self):
+        """Raise NumericalError if a fold fit was truncated; the outputs are NaN already."""
+        G = self.nlam.shape[0]
+        bad = np.flatnonzero(self.npass.cpu().numpy()[G:] < 0).tolist()
+        if bad:
+            from ..utils.guards import NumericalError
+            raise NumericalError(f"binomial CV fold fit(s) {bad} timed out waiting for their "
+                                 "group's lambda sequence; selection is invalid")
+        return self
+
+
+def _group_folds(full_sets, nseg):
+    """full_sets as a list (groups) of lists (folds) of segment tuples; an integer is a fold
+    of one segment. A group's training set is the union of its folds."""
+    groups = []
+    for fs in full_sets:
+        folds = [tuple(sorted({int(f)} if np.isscalar(f) else {int(x) for x in f})) for f in fs]
+        flat = [x for f in folds for x in f]
+        if len(folds) < 2 or any(not f for f in folds):
+            raise ValueError("every group needs at least 2 non-empty folds")
+        if len(set(flat)) != len(flat) or min(flat) < 0 or max(flat) >= nseg:
+            raise ValueError(f"a group's folds must be disjoint sets of segments in [0, {nseg})")
+        groups.append(folds)
+    if not groups:
+        raise ValueError("full_sets is empty")
+    return groups
+
+
+def cv_lognet_groups(panel, xcols, ycol, full_sets, penalty_factor=None, alpha=1.0, nlambda=100,
+                     lambda_min_ratio=None, thresh=1e-7, maxit=100000) -> LognetGroupsResult:
+    """G independent cv.glmnet(family="binomial") fits on one panel in one path launch.
+
+    full_sets: per group the list of its CV folds, each a tuple of panel segments (the
+    arm-split panel: fold j = segments (2j, 2j + 1)). Group g trains on the union of its
+    folds with its own lambda sequence and ratio (glmnet's 1e-4 / 1e-2 rule on its own n vs
+    p); its fold fits leave one fold out and follow that sequence through device flags
+    (csrc/lognet.hip ``ate_lognet_path_groups``: problems 0..G-1 the full fits, then the fold
+    fits group by group). The held-out deviance is one mean over the rows of a fold's
+    segments (``ate_lognet_cvloss_set``); the selection is ``ate_cv_select``. No host
+    synchronisation and no upload after the first call of a layout: capturable. CPU tensors
+    run reference/glmnet.py per group on the same rows and folds.
+    Limits (ValueError): p <= 96, an fp32/fp64 panel, <= 64 segments, <= 256 problems."""
+    nseg = panel.nseg
+    p = len(xcols)
+    groups = _group_folds(full_sets, nseg)
+    G = len(groups)
+    nreal = np.asarray(panel.seg_nreal, dtype=np.int64)
+    ntrain = [int(sum(nreal[list(f)].sum() for f in folds)) for folds in groups]
+    flmin = [float(lambda_min_ratio) if lambda_min_ratio is not None else
+             (1e-4 if n > p else 1e-2) for n in ntrain]
+    vp = _rescale_vp(penalty_factor, p)
+    L = int(nlambda)
+    if not panel.data.is_cuda:
+        return _cv_groups_cpu(panel, xcols, ycol, groups, vp, alpha, L, flmin, thresh, maxit)
+    nprob = G + sum(len(folds) for folds in groups)
+    if p > MAX_P:
+        raise ValueError(f"device lognet supports p <= {MAX_P}, got {p}")
+    if panel.data.dtype not in (torch.float32, torch.float64):
+        raise ValueError("device lognet needs an fp32/fp64 panel")
+    if nseg > MAX_SEGMENTS:
+        raise ValueError(f"device lognet supports <= {MAX_SEGMENTS} segments, got {nseg}")
+    if nprob > MAX_PATH_PROBLEMS:
+        raise ValueError(f"{nprob} path problems, more than the {MAX_PATH_PROBLEMS} one "
+                         "concurrent launch holds")
+    if L < 3:
+        raise ValueError("the concurrent path needs nlambda >= 3")
+    dev = panel.device
+    s = torch.cuda.current_stream().cuda_stream
+    f64 = dict(dtype=torch.float64, device=dev)
+    # problems: the G leaders, then every group's fold fits; hold: the fold fits' held-out sets
+    nq = nprob - G
+    masks = np.zeros((nprob, nseg), dtype=np.uint8)
+    hold = np.zeros((nq, nseg), dtype=np.uint8)
+    leader = np.arange(nprob, dtype=np.int32)
+    Kmax = max(len(folds) for folds in groups)
+    if any(len(folds) != Kmax for folds in groups):
+        raise ValueError("every group needs the same number of folds")
+    fidx = np.zeros((G, Kmax), dtype=np.int32)
+    nfold = np.zeros((G, Kmax), dtype=np.float64)
+    q = 0
+    for g, folds in enumerate(groups):
+        train = [x for f in folds for x in f]
+        masks[g, train] = 1
+        for i, f in enumerate(folds):
+            masks[G + q, train] = 1
+            masks[G + q, list(f)] = 0
+            hold[q, list(f)] = 1
+            leader[G + q] = g
+            fidx[g, i] = q
+            nfold[g, i] = nreal[list(f)].sum()
+            q += 1
+    segs = np.stack([panel.seg_bounds[:, 0], panel.seg_bounds[:, 0] + panel.seg_nreal], 1)
+    segs_t = const(segs.astype(np.int64), torch.int64, dev)
+    xc = const(np.asarray(xcols), torch.int32, dev)
+    vp_t = const(vp, torch.float64, dev)
+    masks_t = const(masks, torch.uint8, dev)
+    hold_t = const(hold, torch.uint8, dev)
+    leader_t = const(leader, torch.int32, dev)
+    flmin_t = const(np.asarray(flmin), torch.float64, dev)
+    fidx_t = const(fidx, torch.int32, dev)
+    nfold_t = const(nfold, torch.float64, dev)
+    a0 = torch.zeros((nprob, L), **f64)
+    beta = torch.zeros((nprob, L, p), **f64)
+    lam = torch.full((nprob, L), float("nan"), **f64)
+    devr = torch.zeros((nprob, L), **f64)
+    nlam = torch.zeros(nprob, dtype=torch.int32, device=dev)
+    npass = torch.zeros(nprob, dtype=torch.int32, device=dev)
+    progress = torch.zeros((G, 2), dtype=torch.int32, device=dev)   # zeroed on every call
+    lampub = torch.zeros((G, L), **f64)
+    dt = dtype_code(panel.data)
+    X = panel.data
+    _native.call("ate_lognet_path_groups", dt, X.data_ptr(), panel.cm_ld, xc.data_ptr(), p, ycol,
+                 segs_t.data_ptr(), nseg, masks_t.data_ptr(), nprob, leader.ctypes.data,
+                 leader_t.data_ptr(), vp_t.data_ptr(), alpha, flmin_t.data_ptr(), thresh, maxit,
+                 L, a0.data_ptr(), beta.data_ptr(), lam.data_ptr(), devr.data_ptr(),
+                 nlam.data_ptr(), npass.data_ptr(), progress.data_ptr(), lampub.data_ptr(), s)
+    cvraw = torch.empty((nq, L), **f64)
+    _native.call("ate_lognet_cvloss_set", dt, X.data_ptr(), panel.cm_ld, xc.data_ptr(), p, ycol,
+                 segs_t.data_ptr(), nseg, hold_t.data_ptr(), nq, a0[G:].data_ptr(),
+                 beta[G:].data_ptr(), nlam[G:].data_ptr(), L, cvraw.data_ptr(), s)
+    cvm = torch.empty((G, L), **f64)
+    cvsd = torch.empty((G, L), **f64)
+    sel = torch.empty((G, 2), dtype=torch.int32, device=dev)
+    _native.call("ate_cv_select", cvraw.data_ptr(), fidx_t.data_ptr(), nfold_t.data_ptr(), Kmax,
+                 G, nlam.data_ptr(), L, cvm.data_ptr(), cvsd.data_ptr(), sel.data_ptr(),
+                 npass[G:].data_ptr(), nq, s)
+    coef = torch.cat([a0[:G, :, None], beta[:G]], 2)                 # [G, L, p+1]
+    sl = sel.long()
+    pick = lambda i: torch.gather(coef, 1, sl[:, i, None, None].expand(G, 1, p + 1))[:, 0]
+    from .enet import poison_if_truncated
+    cmin, c1se = poison_if_truncated(npass[G:], pick(0), pick(1))
+    return LognetGroupsResult(lam[:G], nlam[:G], cvm, cvsd, sel, cmin, c1se, npass)
+
+
+def _cv_groups_cpu(panel, xcols, ycol, groups, vp, alpha, L, flmin, thresh, maxit):
+    X = panel.data.double()
+    G, p = len(groups), len(xcols)
+    nan = lambda *sh: torch.full(sh, float("nan"), dtype=torch.float64)
+    lam, cvm, cvsd = nan(G, L), nan(G, L), nan(G, L)
+    cmin, c1se = nan(G, p + 1), nan(G, p + 1)
+    sel = torch.zeros((G, 2), dtype=torch.int32)
+    nlam = torch.zeros(G, dtype=torch.int32)
+    npass = torch.zeros(G, dtype=torch.int32)
+    for g, folds in enumerate(groups):
+        rows, fid = [], []
+        for i, f in enumerate(folds):
+            for sgm in f:
+                r0, nr = int(panel.seg_bounds[sgm][0]), int(panel.seg_nreal[sgm])
+                rows.append(np.arange(r0, r0 + nr))
+                fid.append(np.full(nr, i))
+        rows = np.concatenate(rows)
+        cv = ref.cv_glmnet(X[xcols][:, rows].T.numpy(), X[ycol][rows].numpy(), family="binomial",
+                           alpha=alpha, penalty_factor=vp, foldid=np.concatenate(fid), nlambda=L,
+                           lambda_min_ratio=flmin[g], thresh=thresh, maxit=maxit)
+        m = len(cv.lambdas)
+        coef = np.column_stack([cv.fit.a0, cv.fit.beta])
+        lam[g, :m] = torch.as_tensor(cv.lambdas)
+        cvm[g, :m] = torch.as_tensor(cv.cvm)
+        cvsd[g, :m] = torch.as_tensor(cv.cvsd)
+        cmin[g] = torch.as_tensor(coef[cv.idx_min])
+        c1se[g] = torch.as_tensor(coef[cv.idx_1se])
+        sel[g, 0], sel[g, 1], nlam[g], npass[g] = cv.idx_min, cv.idx_1se, m, cv.fit.npasses
+    return LognetGroupsResult(lam, nlam, cvm, cvsd, sel, cmin, c1se, npass)

@@ -347,9 +347,23 @@ def dml_plr_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min",
     return dml_from_residuals(yr, wr, method)
 
 
-def _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids=None):
+PROPENSITIES = ("linear", "logit")
+
+
+def check_propensity(propensity) -> str:
+    """The propensity fit of the interactive model: "linear" (the linear-probability gaussian
+    LASSO, clipped) or "logit" (the binomial LASSO, cv.glmnet(family="binomial"))."""
+    if propensity not in PROPENSITIES:
+        raise ValueError(f"propensity must be one of {PROPENSITIES}, got {propensity!r}")
+    return propensity
+
+
+def _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids=None, propensity="linear"):
     """The held-out nuisances and per-row AIPW scores of the cross-fitted interactive model
-    (validated inputs as float64 arrays): (psi, g0, g1, m), m before clipping."""
+    (validated inputs as float64 arrays): (psi, g0, g1, m), m before clipping. propensity
+    "logit": m is the predicted response of the binomial LASSO on the same training rows and
+    inner folds."""
+    logit = check_propensity(propensity) == "logit"
     if not np.isin(W, (0.0, 1.0)).all():
         raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
     fid = rng.fold_ids(len(Y), folds, seed, stream=0) if fold_ids is None else \
@@ -367,7 +381,8 @@ def _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids=None):
         inner = np.where(fid > k, fid - 1, fid)
         for rows, target, out in (((~te) & (W == 0), Y, g0), ((~te) & (W == 1), Y, g1),
                                   (~te, W, m)):
-            cv = gn.cv_glmnet(X[rows], target[rows], foldid=inner[rows])
+            family = "binomial" if logit and out is m else "gaussian"
+            cv = gn.cv_glmnet(X[rows], target[rows], family=family, foldid=inner[rows])
             out[te] = cv.predict(X[te], s=s)
     e = np.clip(m, clip, 1 - clip)
     psi = g1 - g0 + W * (Y - g1) / e - (1 - W) * (Y - g0) / (1 - e)
@@ -375,7 +390,7 @@ def _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids=None):
 
 
 def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
-                  method="DML-IRM cross-fit (LASSO)", fold_ids=None):
+                  method="DML-IRM cross-fit (LASSO)", fold_ids=None, propensity="linear"):
     """Cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1) with
     CV-LASSO nuisances, row by row in float64: for held-out fold k, g0 and g1 are gaussian
     LASSO fits of Y on the training rows of each arm and m is the linear-probability LASSO of
@@ -384,10 +399,11 @@ def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
     - (1 - W)(Y - g0) / (1 - m) with m clipped to [clip, 1 - clip]; theta = mean(psi),
     SE = sd(psi) / sqrt(n)."""
     Y, W, X = _arr(Y), _arr(W), _arr(X)
-    psi, g0, g1, m = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    psi, g0, g1, m = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids, propensity)
     n = len(Y)
     nt = W.sum()
-    return AteResult.make(method, psi.mean(), psi.std(ddof=1) / np.sqrt(n), n=n,
+    extra = {} if propensity == "linear" else {"propensity": propensity}
+    return AteResult.make(method, psi.mean(), psi.std(ddof=1) / np.sqrt(n), n=n, **extra,
                           n_clipped=int(((m < clip) | (m > 1 - clip)).sum()),
                           n_treated=int(nt),
                           rmse_g0=float(np.sqrt(((1 - W) * (Y - g0) ** 2).sum() / (n - nt))),
@@ -430,7 +446,7 @@ def gate_from_scores(psi, codes, n_groups, n_boot=999, level=0.95, seed=1991, ro
 
 def dml_irm_gate(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", clip=0.01, n_boot=999,
                  level=0.95, method="DML-IRM group ATEs (LASSO)", fold_ids=None,
-                 keep_boot=False):
+                 keep_boot=False, propensity="linear"):
     """Group average treatment effects of the cross-fitted interactive model with a
     simultaneous confidence band (the float64 twin of estimators.gate.dml_irm_gate_lasso):
     the scores of dml_irm_lasso, averaged within the groups of ``groups`` (one per distinct
@@ -450,7 +466,7 @@ def dml_irm_gate(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", clip=0.
     for g, c in enumerate(np.bincount(codes, minlength=len(labels))):
         if c < 2:
             raise ValueError(f"group {g} has {int(c)} row(s): every group needs at least 2")
-    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids, propensity)
     ng, theta, se, crit, A, Z = gate_from_scores(psi, codes, len(labels), n_boot, level, seed)
     n = len(Y)
     overall = AteResult.make("DML-IRM cross-fit (LASSO)", psi.mean(),
@@ -532,7 +548,8 @@ def cate_from_scores(psi, x, knots, degree, grid, n_boot=999, level=0.95, seed=1
 
 def dml_irm_cate(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boot=999, level=0.95,
                  folds=5, seed=1991, lambda_rule="min", clip=0.01,
-                 method="DML-IRM CATE curve (LASSO)", fold_ids=None, keep_boot=False):
+                 method="DML-IRM CATE curve (LASSO)", fold_ids=None, keep_boot=False,
+                 propensity="linear"):
     """The CATE curve of the cross-fitted interactive model along one covariate with a uniform
     confidence band (the float64 twin of estimators.cate.dml_irm_cate_lasso): the scores of
     dml_irm_lasso projected on a B-spline basis of ``by`` (a column index into X, or an (n,)
@@ -579,7 +596,7 @@ def dml_irm_cate(Y, W, X, by, df=5, degree=3, knots=None, grid=None, n_boot=999,
         if c < 2:
             raise ValueError(f"span {s} of the knot vector has {int(c)} row(s): every span "
                              "needs at least 2")
-    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids, propensity)
     r = cate_from_scores(psi, x, t, q, grid, n_boot, level, seed)
     overall = AteResult.make("DML-IRM cross-fit (LASSO)", psi.mean(),
                              psi.std(ddof=1) / np.sqrt(n), n=n)
@@ -672,7 +689,8 @@ def policy_tree_from_scores(r, Xf, edges, train=None, depth=2, min_leaf=1):
 
 def dml_irm_policy_tree(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.0, train=None,
                         folds=5, seed=1991, lambda_rule="min", clip=0.01,
-                        method="DML-IRM policy tree (LASSO)", fold_ids=None):
+                        method="DML-IRM policy tree (LASSO)", fold_ids=None,
+                        propensity="linear"):
     """The exact policy tree on the AIPW scores of the cross-fitted interactive model (the
     float64 twin of estimators.policy.dml_irm_policy_lasso): the scores of dml_irm_lasso less
     ``cost``, the columns ``features`` of X cut at every distinct value but the smallest (at
@@ -710,7 +728,7 @@ def dml_irm_policy_tree(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.
         else:
             xs = np.sort(X[:, j])
             edges.append(np.unique([xs[(k * n) // int(bins)] for k in range(1, int(bins))]))
-    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids, propensity)
     rec, fin, e = policy_tree_from_scores(psi - float(cost), X[:, f], edges, tr, depth, min_leaf)
     return PolicyTreeResult.make(method, rec, fin, f, edges, float(cost), int(depth),
                                  held_out=train is not None, hipgraph=False, e=int(e),
@@ -850,7 +868,7 @@ def targets_from_rows(y, w, g0, g1, m, clip):
 
 def dml_irm_targets(Y, W, X, targets=("all", "treated", "control"), folds=5, seed=1991,
                     lambda_rule="min", clip=0.01, method="DML-IRM target populations (LASSO)",
-                    fold_ids=None, repeats=1):
+                    fold_ids=None, repeats=1, propensity="linear"):
     """The average effect of the cross-fitted interactive model over everyone, on the
     treated (ATT) and on the controls (ATC) with their joint covariance, the float64 twin of
     estimators.targets.dml_irm_targets: per-row nuisances from _irm_scores (all three are
@@ -862,7 +880,7 @@ def dml_irm_targets(Y, W, X, targets=("all", "treated", "control"), folds=5, see
         raise ValueError("repeated cross-fitting is not available for the target populations: "
                          "repeats must be 1")
     Y, W, X = _arr(Y), _arr(W), _arr(X)
-    _, g0, g1, m = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids)
+    _, g0, g1, m = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids, propensity)
     theta, cov = targets_from_rows(Y, W, g0, g1, m, clip)
     return TargetResult.from_estimates(method, theta, cov, targets, n=len(Y),
                                        n_treated=int(W.sum()),

@@ -37,6 +37,11 @@ namespace {
 // populations (ate_irm_target_moments below).
 enum Mode { MOMENTS = 0, ROWS = 1, SENS = 2, TARGETS = 3 };
 
+// What the third coefficient row predicts: the propensity itself (the linear-probability
+// fit) or its logit (the binomial fit of csrc/lognet.hip): m = 1 / (1 + exp(-eta)) in fp64,
+// before the score sees it, so n_clipped and S (w - m)^2 are about the probability.
+enum Link { IDENTITY = 0, LOGISTIC = 1 };
+
 constexpr int NM = 8;    // moments of MOMENTS
 constexpr int NS = 14;   // moments of SENS
 constexpr int NT = 12;   // moments of TARGETS
@@ -156,8 +161,8 @@ __device__ __forceinline__ void irm_accumulate(double (&v)[NT], double y, double
 // fp32 / fp64 column-major panels: fp64 dot products, RPT rows per thread 256 apart.
 // MODE ROWS: `partial` is psi[ld] instead -- every row of the segment gets its score (0 on a
 // padding row) and no moment is accumulated (ate_irm_scores). SENS: the 14 moments; TARGETS:
-// the 12 moments.
-template <typename T, int RPT, int MODE>
+// the 12 moments. LINK: the link of the propensity row (fp32 / fp64 panels only).
+template <typename T, int RPT, int MODE, int LINK>
 __global__ __launch_bounds__(256) void irm_score_kernel(
     const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p, int P,
     const Seg* __restrict__ segs, int nseg, int spf,
@@ -221,8 +226,9 @@ __global__ __launch_bounds__(256) void irm_score_kernel(
       const double y = ld_col(X, ld, y0, ii[r]) + (y1 >= 0 ? ld_col(X, ld, y1, ii[r]) : 0.0);
       const double w = ld_col(X, ld, w0, ii[r]) + (w1 >= 0 ? ld_col(X, ld, w1, ii[r]) : 0.0);
       ATE_DASSERT(spf != 2 || w == (double)(s & 1));
-      if (MODE == ROWS) partial[ii[r]] = irm_psi(y, w, a0[r], a1[r], am[r], clip);
-      else irm_accumulate(v, y, w, a0[r], a1[r], am[r], clip);
+      const double m = LINK == LOGISTIC ? 1.0 / (1.0 + exp(-am[r])) : am[r];
+      if (MODE == ROWS) partial[ii[r]] = irm_psi(y, w, a0[r], a1[r], m, clip);
+      else irm_accumulate(v, y, w, a0[r], a1[r], m, clip);
     }
   }
   if (MODE != ROWS) write_partial<N>(v, red, partial);
@@ -310,11 +316,11 @@ __global__ __launch_bounds__(256) void irm_score_bf16_kernel(
   if (MODE != ROWS) write_partial<N>(v, red, partial);
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, int LINK>
 int irm_score_t(const void* X, int64_t ld, const void* xcols, int p, int P, const void* segs,
                 int nseg, int spf, const void* coef, int y0, int y1, int w0, int w1, int vcol,
                 double clip, int nbx, void* partial, size_t sh, hipStream_t s) {
-  ATE_LAUNCH((irm_score_kernel<T, 4, MODE>), dim3(nbx, nseg), dim3(256), sh, s, (const T*)X, ld,
+  ATE_LAUNCH((irm_score_kernel<T, 4, MODE, LINK>), dim3(nbx, nseg), dim3(256), sh, s, (const T*)X, ld,
              (const int*)xcols, p, P, (const Seg*)segs, nseg, spf, (const double*)coef, y0, y1,
              w0, w1, vcol, clip, (double*)partial);
   ATE_CHECK_LAUNCH();
@@ -323,12 +329,13 @@ int irm_score_t(const void* X, int64_t ld, const void* xcols, int p, int P, cons
 
 // The score pass of every entry point (argument checks and the launch): ROWS writes psi[ld]
 // through `out`, otherwise `out` is the partial buffer [nseg*nbx][8] (SENS: [14], TARGETS:
-// [12]) of the moment pass.
+// [12]) of the moment pass. link: IDENTITY or LOGISTIC (fp32 / fp64 panels only).
 template <int MODE>
-int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols, int p,
+int irm_pass(int link, int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols, int p,
              const void* segs, int nseg, int segs_per_fold, const void* coef, int y0, int y1,
              int w0, int w1, int vcol, double clip, int nbx, void* out, hipStream_t s) {
   if (dtype < 1 || dtype > 3 || (dtype != 3 && bs != 64)) return -1;
+  if ((link != IDENTITY && link != LOGISTIC) || (link == LOGISTIC && dtype == 3)) return -1;
   if (p < 0 || nseg < 1 || nseg > 65535 || segs_per_fold < 1 || nbx < 1 || cs < 64 || bs < 64)
     return -1;
   if (y0 < 0 || w0 < 0 || vcol < 0) return -1;
@@ -343,12 +350,14 @@ int irm_pass(int dtype, const void* X, int64_t cs, int64_t bs, const void* xcols
   // most 1856 (SENS, N = 14; TARGETS, N = 12: 1600)
   static_assert(16 * nmom<MODE>() * sizeof(double) + 64 <= 2048, "static LDS of the pass");
   if (sh > 64 * 1024 - 2048) return -1;
-  if (dtype == 1)
-    return irm_score_t<float, MODE>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
-                                    w0, w1, vcol, clip, nbx, out, sh, s);
-  if (dtype == 2)
-    return irm_score_t<double, MODE>(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1,
-                                     w0, w1, vcol, clip, nbx, out, sh, s);
+  if (dtype != 3) {
+    auto f = dtype == 1 ? (link == LOGISTIC ? irm_score_t<float, MODE, LOGISTIC>
+                                            : irm_score_t<float, MODE, IDENTITY>)
+                        : (link == LOGISTIC ? irm_score_t<double, MODE, LOGISTIC>
+                                            : irm_score_t<double, MODE, IDENTITY>);
+    return f(X, cs, xcols, p, P, segs, nseg, segs_per_fold, coef, y0, y1, w0, w1, vcol, clip, nbx,
+             out, sh, s);
+  }
   ATE_LAUNCH(irm_score_bf16_kernel<MODE>, dim3(nbx, nseg), dim3(256), sh, s, (const bf16_t*)X, cs,
              bs, (const int*)xcols, p, P, ld, (const Seg*)segs, nseg, segs_per_fold,
              (const double*)coef, y0, y1, w0, w1, vcol, clip, (double*)out);
@@ -646,7 +655,7 @@ ATE_API int ate_irm_score_moments(int dtype, const void* X, int64_t cs, int64_t 
                                   int w1, int vcol, double clip, int nbx, void* partial,
                                   void* moments, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int rc = irm_pass<MOMENTS>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0,
+  const int rc = irm_pass<MOMENTS>(IDENTITY, dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0,
                                  y1, w0, w1, vcol, clip, nbx, partial, s);
   if (rc != 0) return rc;
   ATE_LAUNCH(irm_sum_kernel<NM>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
@@ -662,7 +671,7 @@ ATE_API int ate_irm_scores(int dtype, const void* X, int64_t cs, int64_t bs, con
                            int p, const void* segs, int nseg, int segs_per_fold,
                            const void* coef, int y0, int y1, int w0, int w1, int vcol,
                            double clip, int nbx, void* psi, void* stream) {
-  return irm_pass<ROWS>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0, y1, w0,
+  return irm_pass<ROWS>(IDENTITY, dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0, y1, w0,
                         w1, vcol, clip, nbx, psi, (hipStream_t)stream);
 }
 
@@ -677,7 +686,7 @@ ATE_API int ate_irm_sens_moments(int dtype, const void* X, int64_t cs, int64_t b
                                  int w1, int vcol, double clip, int nbx, void* partial,
                                  void* moments, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int rc = irm_pass<SENS>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0,
+  const int rc = irm_pass<SENS>(IDENTITY, dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0,
                                 y1, w0, w1, vcol, clip, nbx, partial, s);
   if (rc != 0) return rc;
   ATE_LAUNCH(irm_sum_kernel<NS>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
@@ -699,11 +708,41 @@ ATE_API int ate_irm_target_moments(int dtype, const void* X, int64_t cs, int64_t
                                    int w1, int vcol, double clip, int nbx, void* partial,
                                    void* moments, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int rc = irm_pass<TARGETS>(dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef,
+  const int rc = irm_pass<TARGETS>(IDENTITY, dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef,
                                    y0, y1, w0, w1, vcol, clip, nbx, partial, s);
   if (rc != 0) return rc;
   ATE_LAUNCH(irm_sum_kernel<NT>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
              (double*)moments);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The four passes above with the link of the propensity row chosen by the caller. mode: 0 the
+// 8 moments, 1 psi per row (`partial` is psi [ld], `moments` unused), 2 the 14 moments of the
+// sensitivity analysis, 3 the 12 moments of the targets. link: 0 identity -- the bits of the
+// entry points above -- or 1 logistic: coefficient row 2 holds logit coefficients and
+// m = 1 / (1 + exp(-eta)) before the score sees it. fp32 / fp64 panels only with link 1.
+ATE_API int ate_irm_score_link(int mode, int link, int dtype, const void* X, int64_t cs,
+                               int64_t bs, const void* xcols, int p, const void* segs, int nseg,
+                               int segs_per_fold, const void* coef, int y0, int y1, int w0, int w1,
+                               int vcol, double clip, int nbx, void* partial, void* moments,
+                               void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (mode < MOMENTS || mode > TARGETS) return -1;
+  auto pass = mode == MOMENTS ? irm_pass<MOMENTS> : mode == ROWS ? irm_pass<ROWS>
+              : mode == SENS  ? irm_pass<SENS> : irm_pass<TARGETS>;
+  const int rc = pass(link, dtype, X, cs, bs, xcols, p, segs, nseg, segs_per_fold, coef, y0, y1,
+                      w0, w1, vcol, clip, nbx, partial, s);
+  if (rc != 0 || mode == ROWS) return rc;
+  if (mode == MOMENTS)
+    ATE_LAUNCH(irm_sum_kernel<NM>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
+               (double*)moments);
+  else if (mode == SENS)
+    ATE_LAUNCH(irm_sum_kernel<NS>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
+               (double*)moments);
+  else
+    ATE_LAUNCH(irm_sum_kernel<NT>, dim3(1), dim3(256), 0, s, (const double*)partial, nbx * nseg,
+               (double*)moments);
   ATE_CHECK_LAUNCH();
   return 0;
 }

@@ -31,6 +31,12 @@
 // its own first pass at lambda m, for the full fit's decision on m: the fold path then
 // ends exactly where the two-launch form (nlam read from the finished full fit) ends, with
 // bit-identical outputs, while the two paths run side by side instead of back to back.
+//
+// Grouped launch (ate_lognet_path_groups): several such cross-validated fits in one launch,
+// e.g. the K outer training sets of a cross-fit with their K - 1 inner folds each. Every
+// problem names its leader; the leaders are the lowest problem indices and each owns a
+// progress pair, a published sequence and a lambda ratio. The protocol is the one above per
+// group; ate_lognet_path in concurrent mode is the one-group case of the same kernel.
 #include "common.hpp"
 
 namespace {
@@ -78,7 +84,8 @@ __global__ __launch_bounds__(NTK) void lognet_path_kernel(
     const double* __restrict__ ulam, const int* __restrict__ nlam_in, int L,
     double* __restrict__ a0_out, double* __restrict__ beta_out, double* __restrict__ lam_out,
     double* __restrict__ dev_out, int* __restrict__ nlam_out, int* __restrict__ npass_out,
-    int* __restrict__ progress, double* __restrict__ lampub) {
+    int* __restrict__ progress, double* __restrict__ lampub, const int* __restrict__ leader,
+    const double* __restrict__ flmin_g) {
   using C = Cfg<PM, NTK>;
   constexpr int Q = C::Q, QP = C::QP, RB = C::RB, TPT = C::TPT, NCH = C::NCH;
   __shared__ double sC[Q * Q];
@@ -98,6 +105,17 @@ __global__ __launch_bounds__(NTK) void lognet_path_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const uint8_t* mk = masks + (int64_t)prob * nseg;
   ATE_DASSERT(p > 0 && p <= PM && nseg > 0 && nseg <= MAXSEG && ycol >= 0 && L > 0);
+  // grouped launch: the problem's leader (itself: a full fit) names its group, whose flags,
+  // published sequence and lambda ratio it uses; without `leader` the launch is one group
+  // led by problem 0
+  const int lead = leader ? leader[prob] : 0;
+  ATE_DASSERT(lead >= 0 && lead <= prob && (!leader || leader[lead] == lead));
+  ATE_DASSERT(!leader || (progress != nullptr && lampub != nullptr && flmin_g != nullptr));
+  if (leader) {
+    progress += 2 * lead;
+    lampub += (int64_t)lead * L;
+    flmin = flmin_g[lead];
+  }
 
   if (tid == 0) {
     int acc = 0, k = 0;
@@ -190,7 +208,7 @@ __global__ __launch_bounds__(NTK) void lognet_path_kernel(
   }
 
   const bool conc = progress != nullptr;
-  const bool have_ulam = conc ? prob > 0 : ulam != nullptr;
+  const bool have_ulam = conc ? prob != lead : ulam != nullptr;
   const int nlam = have_ulam && !conc ? (nlam_in ? *nlam_in : L) : L;
   const double alf = have_ulam ? 1.0 : pow(flmin, 1.0 / (double)(nlam - 1));
   const double shr = thresh * dev0;
@@ -543,24 +561,65 @@ __global__ __launch_bounds__(NT) void lognet_cvloss_kernel(
   if (threadIdx.x == 0) cvraw[(int64_t)k * L + m] = -2.0 * acc[0] / (double)(r1 - r0);
 }
 
+// held-out binomial deviance over a SET of segments: cvraw[k][m] = mean over the rows of the
+// segments s with hold[k][s] != 0 (ascending s; one mean over the rows of all of them) of
+// problem k's fit at lambda m; NaN past nlam[k]
+template <typename T>
+__global__ __launch_bounds__(NT) void lognet_cvloss_set_kernel(
+    const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p, int ycol,
+    const int64_t* __restrict__ segs, int nseg, const uint8_t* __restrict__ hold,
+    const double* __restrict__ a0, const double* __restrict__ beta, const int* __restrict__ nlam,
+    int L, double* __restrict__ cvraw) {
+  __shared__ double red[16];
+  const int k = blockIdx.x, m = blockIdx.y;
+  ATE_DASSERT(m < L && nseg > 0 && nseg <= MAXSEG);
+  if (m >= nlam[k]) {
+    if (threadIdx.x == 0) cvraw[(int64_t)k * L + m] = __builtin_nan("");
+    return;
+  }
+  const double* b = beta + ((int64_t)k * L + m) * p;
+  const double b0 = a0[(int64_t)k * L + m];
+  double acc[1] = {0.0};
+  int64_t rows = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (!hold[(int64_t)k * nseg + s]) continue;
+    const int64_t r0 = segs[2 * s], r1 = segs[2 * s + 1];
+    ATE_DASSERT(r0 >= 0 && r0 <= r1 && r1 <= ld);
+    rows += r1 - r0;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += NT) {
+      double eta = b0;
+      for (int j = 0; j < p; ++j) eta += (double)X[(int64_t)xcols[j] * ld + r] * b[j];
+      const double q = clampq(eta);
+      const double y = (double)X[(int64_t)ycol * ld + r];
+      acc[0] += y * log(q) + (1.0 - y) * log(1.0 - q);
+    }
+  }
+  ate::block_sum<1>(acc, red);
+  if (threadIdx.x == 0) cvraw[(int64_t)k * L + m] = -2.0 * acc[0] / (double)rows;
+}
+
 template <typename T>
 int launch_path(const void* X, int64_t ld, const int* xcols, int p, int ycol, const int64_t* segs,
                 int nseg, const uint8_t* masks, int nprob, const double* vp, double alpha,
                 double flmin, double thresh, int maxit, const double* ulam, const int* nlam_in,
                 int L, double* a0, double* beta, double* lam, double* dev, int* nlam_out,
-                int* npass, int* progress, double* lampub, hipStream_t st) {
+                int* npass, int* progress, double* lampub, const int* leader,
+                const double* flmin_g, hipStream_t st) {
   if (p <= 24)
     ATE_LAUNCH((lognet_path_kernel<T, 24, 512>), dim3(nprob), dim3(512), 0, st, (const T*)X,
                        ld, xcols, p, ycol, segs, nseg, masks, vp, alpha, flmin, thresh, maxit, ulam,
-                       nlam_in, L, a0, beta, lam, dev, nlam_out, npass, progress, lampub);
+                       nlam_in, L, a0, beta, lam, dev, nlam_out, npass, progress, lampub, leader,
+                       flmin_g);
   else if (p <= 32)
     ATE_LAUNCH((lognet_path_kernel<T, 32, NT>), dim3(nprob), dim3(NT), 0, st, (const T*)X, ld,
                        xcols, p, ycol, segs, nseg, masks, vp, alpha, flmin, thresh, maxit, ulam,
-                       nlam_in, L, a0, beta, lam, dev, nlam_out, npass, progress, lampub);
+                       nlam_in, L, a0, beta, lam, dev, nlam_out, npass, progress, lampub, leader,
+                       flmin_g);
   else
     ATE_LAUNCH((lognet_path_kernel<T, 96, NT>), dim3(nprob), dim3(NT), 0, st, (const T*)X, ld,
                        xcols, p, ycol, segs, nseg, masks, vp, alpha, flmin, thresh, maxit, ulam,
-                       nlam_in, L, a0, beta, lam, dev, nlam_out, npass, progress, lampub);
+                       nlam_in, L, a0, beta, lam, dev, nlam_out, npass, progress, lampub, leader,
+                       flmin_g);
   return 0;
 }
 
@@ -570,6 +629,8 @@ ATE_KERNEL_SHAPE("lognet_path_kernel<double, 24>", 512, 0, lognet_path_kernel<do
 ATE_KERNEL_SHAPE("lognet_path_kernel<float, 24>", 512, 0, lognet_path_kernel<float, 24, 512>)
 ATE_KERNEL_SHAPE("lognet_path_kernel<double, 32>", NT, 0, lognet_path_kernel<double, 32, NT>)
 ATE_KERNEL_SHAPE("lognet_path_kernel<double, 96>", NT, 0, lognet_path_kernel<double, 96, NT>)
+ATE_KERNEL_SHAPE("lognet_cvloss_set_kernel<double>", NT, 0, lognet_cvloss_set_kernel<double>)
+ATE_KERNEL_SHAPE("lognet_cvloss_set_kernel<float>", NT, 0, lognet_cvloss_set_kernel<float>)
 
 // dt: 1 = fp32 panel, 2 = fp64 panel. segs: int64 [nseg][2] real-row ranges.
 ATE_API int ate_lognet_path(int dt, const void* X, int64_t ld, const void* xcols, int p, int ycol,
@@ -586,7 +647,42 @@ ATE_API int ate_lognet_path(int dt, const void* X, int64_t ld, const void* xcols
   f(X, ld, (const int*)xcols, p, ycol, (const int64_t*)segs, nseg, (const uint8_t*)masks, nprob,
     (const double*)vp, alpha, flmin, thresh, maxit, (const double*)ulam, (const int*)nlam_in, L,
     (double*)a0, (double*)beta, (double*)lam, (double*)dev, (int*)nlam_out, (int*)npass,
-    (int*)progress, (double*)lampub, st);
+    (int*)progress, (double*)lampub, nullptr, nullptr, st);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// Several cross-validated fits in ONE concurrent launch. leader_host / leader: int32 [nprob],
+// the same values on the host (checked here) and on the device (read by the kernel): a
+// problem whose leader is itself is a full fit with its own lambda sequence, any other is a
+// fold fit that follows its leader's. The leaders are problems 0 .. ngroups-1 and number the
+// groups (workgroups dispatch in index order: a leader never queues behind a spinning
+// follower). Per group g: progress [ngroups][2] int32 (zeroed by the caller), lampub
+// [ngroups][L], flmin [ngroups] (glmnet's ratio depends on each training set's n vs p).
+// Every other argument as ate_lognet_path in concurrent mode; outputs per problem.
+ATE_API int ate_lognet_path_groups(int dt, const void* X, int64_t ld, const void* xcols, int p,
+                                   int ycol, const void* segs, int nseg, const void* masks,
+                                   int nprob, const void* leader_host, const void* leader,
+                                   const void* vp, double alpha, const void* flmin, double thresh,
+                                   int maxit, int L, void* a0, void* beta, void* lam, void* dev,
+                                   void* nlam_out, void* npass, void* progress, void* lampub,
+                                   void* stream) {
+  if (p < 1 || p > 96 || nseg < 1 || nseg > MAXSEG || (dt != 1 && dt != 2)) return -1;
+  if (nprob < 1 || nprob > 256 || L < 3) return -1;
+  if (!leader_host || !leader || !flmin || !progress || !lampub) return -1;
+  const int* lh = (const int*)leader_host;
+  int ngroups = 0;
+  for (int q = 0; q < nprob; ++q) ngroups += lh[q] == q;
+  for (int q = 0; q < nprob; ++q) {
+    // a leader behind a follower, or a follower of a problem that is no leader
+    if (q < ngroups ? lh[q] != q : (lh[q] < 0 || lh[q] >= ngroups)) return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  auto f = dt == 2 ? launch_path<double> : launch_path<float>;
+  f(X, ld, (const int*)xcols, p, ycol, (const int64_t*)segs, nseg, (const uint8_t*)masks, nprob,
+    (const double*)vp, alpha, 0.0, thresh, maxit, nullptr, nullptr, L, (double*)a0,
+    (double*)beta, (double*)lam, (double*)dev, (int*)nlam_out, (int*)npass, (int*)progress,
+    (double*)lampub, (const int*)leader, (const double*)flmin, st);
   ATE_CHECK_LAUNCH();
   return 0;
 }
@@ -608,6 +704,27 @@ ATE_API int ate_lognet_cvloss(int dt, const void* X, int64_t ld, const void* xco
                        (const int*)xcols, p, ycol, (const int64_t*)segs, (const int*)hold,
                        (const double*)a0, (const double*)beta, (const int*)nlam, L,
                        (double*)cvraw);
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// ate_lognet_cvloss with a set of held-out segments per problem: hold uint8 [nprob][nseg]
+// (the arm-split panel: a fold is two segments).
+ATE_API int ate_lognet_cvloss_set(int dt, const void* X, int64_t ld, const void* xcols, int p,
+                                  int ycol, const void* segs, int nseg, const void* hold,
+                                  int nprob, const void* a0, const void* beta, const void* nlam,
+                                  int L, void* cvraw, void* stream) {
+  if ((dt != 1 && dt != 2) || nseg < 1 || nseg > MAXSEG || nprob < 1 || L < 1) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid(nprob, L);
+  if (dt == 2)
+    ATE_LAUNCH(lognet_cvloss_set_kernel<double>, grid, dim3(NT), 0, st, (const double*)X, ld,
+               (const int*)xcols, p, ycol, (const int64_t*)segs, nseg, (const uint8_t*)hold,
+               (const double*)a0, (const double*)beta, (const int*)nlam, L, (double*)cvraw);
+  else
+    ATE_LAUNCH(lognet_cvloss_set_kernel<float>, grid, dim3(NT), 0, st, (const float*)X, ld,
+               (const int*)xcols, p, ycol, (const int64_t*)segs, nseg, (const uint8_t*)hold,
+               (const double*)a0, (const double*)beta, (const int*)nlam, L, (double*)cvraw);
   ATE_CHECK_LAUNCH();
   return 0;
 }

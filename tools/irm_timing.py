@@ -34,7 +34,15 @@ x{--iivm-col} as the treatment taken (removed from the covariates): one captured
 ``late_phases`` call and one captured ``irm_phases`` call, alternated; then the 15-moment pass
 (``ate_iivm_moments``) and the 8-moment pass on the coefficients of those fits, alternated in
 batches as for ``--targets``. The JSON line carries both union sizes and the bytes each pass
-reads. Recorded in profiles/iivm/README.md."""
+reads. Recorded in profiles/iivm/README.md.
+
+``--propensity logit``: the binomial CV-LASSO propensity (fp32 / fp64 panels, p <= 96) beside
+the linear one on the same arm-split panel: one captured ``irm_phases`` call each, alternated;
+the grouped path launch of ``cv_lognet_groups`` (K * K problems, one launch) beside what there
+was without it, K ``cv_lognet`` calls back to back on the K training panels (plain K-fold
+panels of the same rows without fold k), alternated; and the logistic-link score pass beside
+the identity one on the same coefficients, alternated in batches as for ``--targets``.
+Recorded in profiles/irm_logit/README.md."""
 import argparse
 import json
 import os
@@ -66,6 +74,8 @@ def main():
                     help="time the LATE of the interactive IV model beside the ATE")
     ap.add_argument("--iivm-col", type=int, default=16,
                     help="--iivm: the exactly-binary covariate x{J} taken as the treatment D")
+    ap.add_argument("--propensity", default="linear", choices=["linear", "logit"],
+                    help="logit: time the binomial CV-LASSO propensity beside the linear one")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -84,6 +94,8 @@ def main():
         return targets(a, n, K, kw)
     if a.iivm:
         return iivm(a, n, K, kw)
+    if a.propensity == "logit":
+        return propensity(a, n, K, kw)
     split = synthetic_panel(n, arm_split=True, **kw)
     torch.cuda.synchronize()
 
@@ -287,6 +299,96 @@ def targets(a, n, K, kw):
     r = TargetResult.from_moments("targets", tar()["mom"].cpu().numpy(), tg)
     out["estimates"] = r.rows()
     out["irm_res"] = ate()["res"].cpu().tolist()
+    print(json.dumps(out))
+
+
+def propensity(a, n, K, kw):
+    import dataclasses
+    import numpy as np
+    import torch
+    from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
+    from ate_replication_causalml_amd.estimators import irm as DI
+    from ate_replication_causalml_amd.ops.gram import plan_slot
+    from ate_replication_causalml_amd.ops.lognet import cv_lognet, cv_lognet_groups
+    from ate_replication_causalml_amd.utils.graphs import SegmentedStep
+    split = synthetic_panel(n, arm_split=True, **kw)
+    plain = synthetic_panel(n, selection=split.selection, **kw)
+    torch.cuda.synchronize()
+    with plan_slot(0):
+        lin = SegmentedStep(DI.irm_phases(split, K, "min", a.clip), graph=True, warmup=1)
+    with plan_slot(1):
+        logit = SegmentedStep(DI.irm_phases(split, K, "min", a.clip, propensity="logit"),
+                              graph=True, warmup=1)
+    for _ in range(a.warmup):
+        lin()
+        logit()
+    torch.cuda.synchronize()
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = f()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    ms = {"linear_call": [], "logit_call": [], "grouped_path": [], "k_launches": [],
+          "pass_identity": [], "pass_logistic": []}
+    for _ in range(a.calls):                      # alternate: both see the same clocks
+        ms["linear_call"].append(timed(lin)[0])
+        ms["logit_call"].append(timed(logit)[0])
+    # the K training panels of the alternative: the plain K-fold panel without fold k
+    keep = [[j for j in range(K) if j != k] for k in range(K)]
+    trains = [dataclasses.replace(plain, seg_bounds=np.asarray(plain.seg_bounds)[kk],
+                                  seg_nreal=np.asarray(plain.seg_nreal)[kk]) for kk in keep]
+    sets = DI.logit_fold_sets(K)
+    wcol = split.cols["W"]
+
+    def grouped():
+        return cv_lognet_groups(split, split.xcols, wcol, sets)
+
+    def k_launches():
+        return [cv_lognet(t, t.xcols, t.cols["W"]) for t in trains]
+
+    for _ in range(a.warmup):
+        g = grouped()
+        kl = k_launches()
+    torch.cuda.synchronize()
+    for _ in range(a.calls):
+        ms["grouped_path"].append(timed(grouped)[0])
+        ms["k_launches"].append(timed(k_launches)[0])
+    same_sel = [g.sel[k].cpu().tolist() == kl[k].sel.cpu().tolist() for k in range(K)]
+    coef = logit()["coef"].clone()
+    torch.cuda.synchronize()
+    nb = max(a.pass_batch, 1)
+
+    def batch(link):
+        def f():
+            for _ in range(nb):
+                out = DI.irm_score_moments(split, coef, a.clip, 2, link=link)
+            return out
+        return f
+
+    for _ in range(a.warmup):
+        batch("identity")()
+        batch("logistic")()
+    torch.cuda.synchronize()
+    for _ in range(a.calls):                      # per launch: a batch's time over its size
+        ms["pass_identity"].append(timed(batch("identity"))[0] / nb)
+        ms["pass_logistic"].append(timed(batch("logistic"))[0] / nb)
+    out = {"n": n, "p": a.p, "folds": K, "dtype": a.dtype, "dgp": a.dgp, "calls": a.calls,
+           "pass_batch": nb, "graphed": [lin.graphed, logit.graphed],
+           "grouped_equals_k_launches_sel": same_sel}
+    for name, v in ms.items():
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "mean_ms": statistics.fmean(v)}
+    out["ratio_logit_over_linear_call"] = out["logit_call"]["median_ms"] / out["linear_call"]["median_ms"]
+    out["ratio_k_launches_over_grouped"] = out["k_launches"]["median_ms"] / out["grouped_path"]["median_ms"]
+    out["ratio_pass_logistic_over_identity"] = (out["pass_logistic"]["median_ms"]
+                                                / out["pass_identity"]["median_ms"])
+    out["linear_res"] = lin()["res"].cpu().tolist()
+    out["logit_res"] = logit()["res"].cpu().tolist()
+    out["logit_mom"] = logit()["mom"].cpu().tolist()
     print(json.dumps(out))
 
 
