@@ -89,6 +89,7 @@ _SIGS = {
     "ate_boot_poisson": "ppluiilipp",
     "ate_enet_prepare": "piipipiipipipppppppp",
     "ate_enet_prepare_fused": "piipipiipipi" + "ppppppp" + "plp",
+    "ate_enet_prepare_fused_clear": "piipipiipipi" + "ppppppp" + "pl" + "pl" + "p",
     "ate_enet_path": "pipiippppidddipppppippp",
     "ate_enet_coef": "ppiiiipppppppp",
     "ate_enet_cvloss_gauss": "pippiipppiiipp",

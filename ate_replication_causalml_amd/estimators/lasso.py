@@ -426,7 +426,7 @@ def dml_phases(pan, folds: int, lambda_rule="min", comm=None, seg_counts=None, G
         cv = fit(st)
         coef = pick(cv)
         if fused_final:
-            mom, res = dml_residual_moments(pan, coef, final=True)
+            mom, res = dml_residual_moments(pan, coef, final=True, done=cv.spare_zero)
             return {**st, "cv": cv, "mom": mom, "res": res}
         return {**st, "cv": cv, "mom": dml_residual_moments(pan, coef)}
 
@@ -654,10 +654,12 @@ def _exact_resid(pan, coef: torch.Tensor, mode: int, sh) -> torch.Tensor:
     return part
 
 
-def dml_residual_moments(pan, coef: torch.Tensor, final: bool = False):
+def dml_residual_moments(pan, coef: torch.Tensor, final: bool = False, done=None):
     """Fused held-out residual pass (csrc/dml.hip) -> 7 fp64 moments. ``final`` (GPU panels):
     the same launch also sums the partials and applies the PLR formula -> (moments, res[2]),
-    the bits of this function followed by ``S.dml_finalize(mom, "plr")``."""
+    the bits of this function followed by ``S.dml_finalize(mom, "plr")``. ``done``: a zero
+    int32 [1] on the device that an earlier launch on the stream cleared and nothing else
+    uses, taken as the launch's arrival counter (default: a fill of its own)."""
     K = coef.shape[0]
     p = len(pan.xcols)
     if not pan.data.is_cuda:
@@ -688,7 +690,8 @@ def dml_residual_moments(pan, coef: torch.Tensor, final: bool = False):
     cs, bs = pan.strides()
     if final:
         res = torch.empty(2, dtype=torch.float64, device=dev)
-        done = torch.zeros(1, dtype=torch.int32, device=dev)     # arrival count of the launch
+        if done is None:
+            done = torch.zeros(1, dtype=torch.int32, device=dev)  # arrival count of the launch
         _native.call("ate_dml_resid_moments_final", dtype_code(pan.data), pan.data.data_ptr(), cs,
                      bs, xc.data_ptr(), p, segs.data_ptr(), K, coef.data_ptr(), y0, y1, w0, w1,
                      pan.cols["one"], nbx, part.data_ptr(), done.data_ptr(), mom.data_ptr(),

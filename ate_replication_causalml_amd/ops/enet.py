@@ -30,7 +30,8 @@ def _stream():
 
 # The launches around the path kernel (csrc/enet.hip). Fused (default): one prepare launch
 # (ate_enet_prepare_fused: statistics, C with its pad columns, g, the NaN lambda table) and
-# one tail launch (ate_enet_cv_tail: coefficients, CV loss, selection, picks). ATE_CV_FUSED=0:
+# one tail launch (ate_enet_cv_tail: coefficients, CV loss, selection, picks); up to 8 segments
+# the prepare also clears the call's counters (ate_enet_prepare_fused_clear). ATE_CV_FUSED=0:
 # the chain of separate launches (two fills, ate_enet_prepare's two, ate_enet_coef,
 # ate_enet_cvloss_gauss, ate_cv_select, ate_enet_pick). Same bits either way
 # (profiles/call_glue). Read at import; estimators/lasso.py follows it for the residual pass.
@@ -53,6 +54,10 @@ class EnetCvResult:
     fold_npass: torch.Tensor | None = None   # [nfold] (< 0: the fold's wait timed out)
     fold_nlam: torch.Tensor | None = None    # [nfold] lambdas each fold path kept (its source's
                                              # count: what it ran ahead of the source is dropped)
+    spare_zero: torch.Tensor | None = None   # [1] int32 zero the fused prepare cleared with the
+                                             # call's counters and nothing here uses: a counter
+                                             # for ONE later launch on the stream (the DML
+                                             # residual pass), which then needs no fill
 
     def check(self):
         """Raise NumericalError if any fold path was truncated (host sync). The device
@@ -83,6 +88,16 @@ def _zeroed(dev, *specs):
     buf = torch.zeros(int(offs[-1]), dtype=torch.uint8, device=dev)
     return [buf[int(o):int(o) + b].view(dt).view(sh)
             for (sh, dt), o, b in zip(specs, offs[:-1], sizes)]
+
+
+def _carved(dev, *specs):
+    """The layout of :func:`_zeroed` in an UNINITIALISED buffer, for a kernel to clear
+    (ate_enet_prepare_fused_clear): (buffer, views)."""
+    sizes = [int(np.prod(sh)) * torch.empty((), dtype=dt).element_size() for sh, dt in specs]
+    offs = np.concatenate([[0], np.cumsum([(b + 255) // 256 * 256 for b in sizes])])
+    buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+    return buf, [buf[int(o):int(o) + b].view(dt).view(sh)
+                 for (sh, dt), o, b in zip(specs, offs[:-1], sizes)]
 
 
 def _rescale_vp(vp, p):
@@ -239,10 +254,14 @@ def _cv_gpu(G, P, nseg, masks, xcols, ycols, p, ny, vp, one, full_probs, fold_pr
         # the path kernel writes every apath row below nlam, the only rows the tail reads,
         # and the fused prepare every element of C (pad columns included): not zeroed
         zspec = [((nq, L), torch.float64), ((nq,), i32), ((nq,), i32), ((nq,), i32), ((nf,), i32)]
-        if not fused_prep:
+        spare = zbuf = None
+        if fused_prep:
+            # the fused prepare clears these itself (and one spare counter): no fill launch
+            zbuf, (rsq, nlam, npass, progress, done, spare) = _carved(dev, *zspec, ((1,), i32))
+            C = torch.empty((nt, p, ldc), dtype=c_dt, device=dev)
+        else:
             zspec.append(((nt, p, ldc), c_dt))
-        rsq, nlam, npass, progress, done, *zc = _zeroed(dev, *zspec)
-        C = zc[0] if zc else torch.empty((nt, p, ldc), dtype=c_dt, device=dev)
+            rsq, nlam, npass, progress, done, C = _zeroed(dev, *zspec)
         apath = torch.empty((nq, L, p), **f64)
     else:
         C, apath, rsq, nlam, npass, progress = _zeroed(
@@ -257,10 +276,11 @@ def _cv_gpu(G, P, nseg, masks, xcols, ycols, p, ny, vp, one, full_probs, fold_pr
     nobs = torch.empty(nt, **f64)
     if fused_prep:
         lams = torch.empty((nq, L), **f64)
-        _native.call("ate_enet_prepare_fused", G.data_ptr(), nseg, P, masks_t.data_ptr(), nt,
-                     xc.data_ptr(), p, one, yc.data_ptr(), ny, C.data_ptr(), c_f32, g.data_ptr(),
-                     xm.data_ptr(), xs.data_ptr(), ju.data_ptr(), ym.data_ptr(), ys.data_ptr(),
-                     nobs.data_ptr(), lams.data_ptr(), nq * L, s)
+        _native.call("ate_enet_prepare_fused_clear", G.data_ptr(), nseg, P, masks_t.data_ptr(),
+                     nt, xc.data_ptr(), p, one, yc.data_ptr(), ny, C.data_ptr(), c_f32,
+                     g.data_ptr(), xm.data_ptr(), xs.data_ptr(), ju.data_ptr(), ym.data_ptr(),
+                     ys.data_ptr(), nobs.data_ptr(), lams.data_ptr(), nq * L, zbuf.data_ptr(),
+                     zbuf.numel() // 4, s)
     else:
         _native.call("ate_enet_prepare", G.data_ptr(), nseg, P, masks_t.data_ptr(), nt,
                      xc.data_ptr(), p, one, yc.data_ptr(), ny, C.data_ptr(), c_f32, g.data_ptr(),
@@ -302,7 +322,7 @@ def _cv_gpu(G, P, nseg, masks, xcols, ycols, p, ny, vp, one, full_probs, fold_pr
                      cvraw.data_ptr(), cvm.data_ptr(), cvsd.data_ptr(), sel.data_ptr(),
                      cmin.data_ptr(), c1se.data_ptr(), fold_npass.data_ptr(), done.data_ptr(), s)
         return EnetCvResult(lams[:nf], nlam[:nf], cvm, cvsd, sel, coef, cmin, c1se, full_keys,
-                            npass[:nf], fold_npass, nlam[nf:])
+                            npass[:nf], fold_npass, nlam[nf:], spare)
     coef = torch.empty((nq, L, p + 1), **f64)
     _native.call("ate_enet_coef", apath.data_ptr(), pr.data_ptr(), nq, p, ny, L,
                  nlam.data_ptr(), xm.data_ptr(), xs.data_ptr(), ju.data_ptr(), ym.data_ptr(),

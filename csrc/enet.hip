@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void enet_prepare_fused_kernel(
     const int* __restrict__ ycols, int ny, CT* __restrict__ C, double* __restrict__ g,
     double* __restrict__ xm, double* __restrict__ xs, unsigned char* __restrict__ ju,
     double* __restrict__ ym, double* __restrict__ ys, double* __restrict__ nobs,
-    double* __restrict__ lams, int64_t nlams) {
+    double* __restrict__ lams, int64_t nlams, unsigned* __restrict__ zero, int64_t nzero) {
   const int tk = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
   const int j0 = tj * PF_TJ, k0 = tk * PF_TK, s0 = blockIdx.z * PF_SCH;
   const int lane = tid & 63, jr = tid >> 6;
@@ -198,6 +198,9 @@ __global__ __launch_bounds__(256) void enet_prepare_fused_kernel(
     const int64_t nb = (int64_t)gridDim.x * gridDim.y * gridDim.z,
                   b = ((int64_t)blockIdx.z * gridDim.y + tj) * gridDim.x + tk;
     for (int64_t e = b * 256 + tid; e < nlams; e += nb * 256) lams[e] = __builtin_nan("");
+    // the zero-initialised block of the launches behind this one on the stream (nzero = 0
+    // without one): no fill launch of its own
+    for (int64_t e = b * 256 + tid; e < nzero; e += nb * 256) zero[e] = 0u;
   }
   __shared__ double s_n[PF_SCH], s_m[PF_SCH][PF_NC], s_s[PF_SCH][PF_NC];
   __shared__ unsigned char s_ju[PF_SCH][PF_NC];
@@ -318,12 +321,13 @@ __global__ __launch_bounds__(256) void enet_prepare_fused_kernel(
 }
 
 // lams: nlams doubles set to NaN (the path launch's lambda table); C need not be zeroed.
-ATE_API int ate_enet_prepare_fused(const void* G, int nseg, int P, const void* masks, int ntrain,
-                                   const void* xcols, int p, int ones_col, const void* ycols,
-                                   int ny, void* C, int c_f32, void* g, void* xm, void* xs,
-                                   void* ju, void* ym, void* ys, void* nobs, void* lams,
-                                   int64_t nlams, void* stream) {
-  if (p < 1 || ntrain < 1 || nseg < 1 || ny < 0) return -1;
+// zero: nzero 32-bit words set to 0 (nullptr / 0: none).
+static int enet_prepare_fused_launch(const void* G, int nseg, int P, const void* masks, int ntrain,
+                                     const void* xcols, int p, int ones_col, const void* ycols,
+                                     int ny, void* C, int c_f32, void* g, void* xm, void* xs,
+                                     void* ju, void* ym, void* ys, void* nobs, void* lams,
+                                     int64_t nlams, void* zero, int64_t nzero, void* stream) {
+  if (p < 1 || ntrain < 1 || nseg < 1 || ny < 0 || nzero < 0 || (nzero > 0 && !zero)) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int ldc = (p + 63) / 64 * 64;   // padded row stride
   dim3 grid(ldc / PF_TK, (p + PF_TJ - 1) / PF_TJ, (ntrain + PF_SCH - 1) / PF_SCH);
@@ -331,14 +335,39 @@ ATE_API int ate_enet_prepare_fused(const void* G, int nseg, int P, const void* m
     ATE_LAUNCH(enet_prepare_fused_kernel<float>, grid, dim3(256), 0, st, (const double*)G, nseg,
                P, (const unsigned char*)masks, ntrain, (const int*)xcols, p, ldc, ones_col,
                (const int*)ycols, ny, (float*)C, (double*)g, (double*)xm, (double*)xs,
-               (unsigned char*)ju, (double*)ym, (double*)ys, (double*)nobs, (double*)lams, nlams);
+               (unsigned char*)ju, (double*)ym, (double*)ys, (double*)nobs, (double*)lams, nlams,
+               (unsigned*)zero, nzero);
   else
     ATE_LAUNCH(enet_prepare_fused_kernel<double>, grid, dim3(256), 0, st, (const double*)G, nseg,
                P, (const unsigned char*)masks, ntrain, (const int*)xcols, p, ldc, ones_col,
                (const int*)ycols, ny, (double*)C, (double*)g, (double*)xm, (double*)xs,
-               (unsigned char*)ju, (double*)ym, (double*)ys, (double*)nobs, (double*)lams, nlams);
+               (unsigned char*)ju, (double*)ym, (double*)ys, (double*)nobs, (double*)lams, nlams,
+               (unsigned*)zero, nzero);
   ATE_CHECK_LAUNCH();
   return 0;
+}
+
+ATE_API int ate_enet_prepare_fused(const void* G, int nseg, int P, const void* masks, int ntrain,
+                                   const void* xcols, int p, int ones_col, const void* ycols,
+                                   int ny, void* C, int c_f32, void* g, void* xm, void* xs,
+                                   void* ju, void* ym, void* ys, void* nobs, void* lams,
+                                   int64_t nlams, void* stream) {
+  return enet_prepare_fused_launch(G, nseg, P, masks, ntrain, xcols, p, ones_col, ycols, ny, C,
+                                   c_f32, g, xm, xs, ju, ym, ys, nobs, lams, nlams, nullptr, 0,
+                                   stream);
+}
+
+// ... and clears the nzero 32-bit words at zero: the counters and R^2 table of the path
+// launch, the tail's arrival counter, a spare counter for the residual pass (ops/enet.py)
+ATE_API int ate_enet_prepare_fused_clear(const void* G, int nseg, int P, const void* masks,
+                                         int ntrain, const void* xcols, int p, int ones_col,
+                                         const void* ycols, int ny, void* C, int c_f32, void* g,
+                                         void* xm, void* xs, void* ju, void* ym, void* ys,
+                                         void* nobs, void* lams, int64_t nlams, void* zero,
+                                         int64_t nzero, void* stream) {
+  return enet_prepare_fused_launch(G, nseg, P, masks, ntrain, xcols, p, ones_col, ycols, ny, C,
+                                   c_f32, g, xm, xs, ju, ym, ys, nobs, lams, nlams, zero, nzero,
+                                   stream);
 }
 
 // ------------------------------------------------------------------ path (one wave / problem)
@@ -356,7 +385,8 @@ constexpr int PMAX = 512;
 #ifdef ENET_PROF
 // cycle accounting per problem (debug builds): [0] pull, [1] recurrence, [2] other,
 // [3] block visits, [4] coordinate updates, [5] pending columns pulled, [6] passes
-__device__ unsigned long long enet_prof[256][32];
+constexpr int PROF_N = 40;   // columns per problem (tools/enet_profile.py documents them)
+__device__ unsigned long long enet_prof[256][PROF_N];
 #define PROF_T(var) const unsigned long long var = wall_clock64()
 #define PROF_ADD(k, v) do { if (tid == 0) sprof[0][k] += (unsigned long long)(v); } while (0)
 #else
@@ -477,13 +507,122 @@ constexpr int S_CAP = S_UNION / (PMAX * 4);  // cached columns (56)
 struct PassS {
   double dlx, rsq;
 };
+// mode S, sslot[k]: the cache slot of coordinate k's column (>= 0), SLOT_NONE, or
+// SLOT_FLIGHT while a helper wave's prefetch of it is under way (the column is not readable
+// yet: a mover reads C's row itself and takes no second slot for it)
+constexpr int SLOT_NONE = -1, SLOT_FLIGHT = -2;
+// slots that helper waves may hold for coordinates that have not moved yet: a mover below
+// the mode-switch point (ENET_S_ENTER ever-moved coordinates) always finds a free slot
+constexpr int S_SPEC = S_CAP - ENET_S_ENTER - 1;
+static_assert(S_SPEC >= 0, "mode S: the column cache holds every mover below the switch point");
+
+// the next free cache slot while fewer than `limit` are taken, else -1 (wave-uniform
+// arguments; lane 0's LDS compare-and-swap, so the count never passes the limit and a slot
+// is handed out once whichever wave asks)
+__device__ __forceinline__ int enet_take_slot(LDS_AS int* sncache, int limit) {
+  int slot = -1;
+  if ((threadIdx.x & 63) == 0) {
+    int cur = __hip_atomic_load(sncache, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    while (cur < limit) {
+      if (__hip_atomic_compare_exchange_strong(sncache, &cur, cur + 1, __ATOMIC_RELAXED,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
+        slot = cur;
+        break;
+      }
+    }
+  }
+  return __builtin_amdgcn_readfirstlane(slot);
+}
+
+// wave 0's own slot (or S_CAP: the cache is full). An add, not the helpers' bounded
+// compare-and-swap: a count pushed past S_CAP by a racing helper only reads as "full", and
+// a full cache never empties.
+__device__ __forceinline__ int enet_take_slot_w0(LDS_AS int* sncache) {
+  int got = S_CAP;
+  if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(
+          sncache, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < S_CAP) {
+    if ((threadIdx.x & 63) == 0)
+      got = __hip_atomic_fetch_add(sncache, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    got = __builtin_amdgcn_readfirstlane(got);
+  }
+  return got;
+}
+
+// ---- mode S, helper waves 1..NW-1 (idle while wave 0 walks a pass): prefetch the Gram
+// columns of the coordinates about to enter, so that the first move of one finds its column
+// in the LDS cache and not an L2-missing row of C on the sequential chain. Helper hw scans
+// the sets hw, hw + NP, .. < T of the state the previous pass left in LDS for coordinates
+// that are eligible, at zero, without a slot, and past the NEXT lambda's threshold
+// (|g| > vp * abr, abr = alpha * lambda * the path's lambda ratio): this lambda's entrants
+// and most of the next one's, a lambda ahead. A hit is claimed (SLOT_NONE -> SLOT_FLIGHT),
+// given a slot while fewer than S_SPEC are held by coordinates yet to move, loaded in the
+// layout enet_pass_s reads, and published in sslot[j] after a workgroup release. Speed only:
+// a column is the same floats wherever a mover reads it. Nothing waits on a helper but the
+// barrier that ends the pass.
+__device__ __noinline__ void enet_prefetch_s(int hw, int T, int ldc, double abr,
+                                             const float* __restrict__ Cf,
+                                             const LDS_AS double* sg, const LDS_AS double* sa,
+                                             const LDS_AS double* svp, const LDS_AS int* sflag,
+                                             LDS_AS int* sslot, LDS_AS float* sccache,
+                                             const LDS_AS int* sever_n, LDS_AS int* sncache,
+                                             LDS_AS unsigned long long* sprof_row) {
+  const int lane = threadIdx.x & 63;
+  const int limit = min(S_CAP, min(*sever_n, S_CAP) + S_SPEC);
+  for (int s = hw; s < T; s += NP) {
+    const int k = s * 64 + lane;
+    const bool hit = (sflag[k] & 1) && sslot[k] == SLOT_NONE && sa[k] == 0.0 &&
+                     fabs(sg[k]) > svp[k] * abr;
+    uint64_t hm = __builtin_amdgcn_ballot_w64(hit);
+    while (hm) {
+      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(
+              sncache, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= limit)
+        return;
+      const int lj = __ffsll((unsigned long long)hm) - 1;
+      hm &= hm - 1;
+      const int j = s * 64 + lj;
+      int claimed = 0;
+      if (lane == 0) {
+        int expect = SLOT_NONE;
+        claimed = __hip_atomic_compare_exchange_strong(sslot + j, &expect, SLOT_FLIGHT,
+                                                       __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      if (!__builtin_amdgcn_readfirstlane(claimed)) continue;   // wave 0 cached it meanwhile
+      const int slot = enet_take_slot(sncache, limit);
+      if (slot < 0) {   // the speculative share filled up: give the claim back
+        if (lane == 0) {
+          int expect = SLOT_FLIGHT;
+          __hip_atomic_compare_exchange_strong(sslot + j, &expect, SLOT_NONE, __ATOMIC_RELAXED,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        return;
+      }
+      ATE_DASSERT(slot < S_CAP && j < T * 64);
+      const float* Cj = Cf + j * ldc;   // j * ldc <= PMAX * PMAX
+      float v[8];
+#pragma unroll
+      for (int s8 = 0; s8 < 8; ++s8) v[s8] = Cj[min(s8, T - 1) * 64 + lane];   // as wave 0
+      LDS_AS float* dst = sccache + slot * PMAX;
+#pragma unroll
+      for (int s8 = 0; s8 < 8; ++s8) dst[(s8 >> 2) * 256 + lane * 4 + (s8 & 3)] = v[s8];
+      // the column's stores land before its slot can be seen
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      if (lane == 0)
+        __hip_atomic_store(sslot + j, slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#ifdef ENET_PROF
+      if (lane == 0) sprof_row[32] += 1ull;   // [32] columns prefetched by helper waves
+#endif
+    }
+  }
+}
 // ---- mode S: small active set (glmnet covariance mode's own design: the Gram columns
 // of the coordinates that have moved are kept on chip). While few coordinates have ever
 // moved, a pass runs in wave 0 alone over ALL p coordinates, lane l holding g, a, vp of
 // coordinates k = s * 64 + l (s = 0..7) in registers: the next coordinate that can move
 // (eligible, and nonzero or |g| > vp * lambda; in index order past the last one) comes
 // from eight ballots, and a move updates all p gradients from the mover's cached column
-// (fetched from C's row j -- C is symmetric -- on its first move). Exactly glmnet's
+// (C's row j -- C is symmetric -- prefetched by a helper wave, enet_prefetch_s, or fetched
+// by wave 0 itself on the first move if no helper got to it). Exactly glmnet's
 // sequential pass (full: every coordinate; active: the ever-moved ones), with every
 // gradient exact at all times: nothing is pending when the problem switches to mode L.
 // fp32 C only; the gradients accumulate in fp64. Returns max d^2 (wave-uniform).
@@ -500,7 +639,7 @@ __device__ __noinline__ PassS enet_pass_s(bool full, int T, int ldc, double ab, 
   const int lane = threadIdx.x & 63;
 #ifdef ENET_PROF
   const long long tps0_ = clock64();
-  unsigned long long nit_ = 0, nfetch_ = 0;
+  unsigned long long nit_ = 0, nfetch_ = 0, nused_ = 0;
 #endif
   double gS[8], aS[8], tS[8];
   int slS[8];
@@ -519,7 +658,6 @@ __device__ __noinline__ PassS enet_pass_s(bool full, int T, int ldc, double ab, 
     if ((f & 1) && (full || (f & 2))) flb |= 1 << s8;
     if (f & 2) flb |= 1 << (8 + s8);
   }
-  int ncache = __builtin_amdgcn_readfirstlane(*sncache);   // uniform (SGPR) counters
   int ever_n = __builtin_amdgcn_readfirstlane(*sever_n);
   double dlx = 0.0, rsq_add = 0.0;
 #ifdef ENET_PROF
@@ -552,24 +690,46 @@ __device__ __noinline__ PassS enet_pass_s(bool full, int T, int ldc, double ab, 
       if (dem != 0.0) an = an / (1.0 + svp[j] * dem);
       const double d = an - aj;
       if (__builtin_amdgcn_readfirstlane((int)(d == 0.0))) continue;
-      // the mover's column: cached, newly cached, or (cache full) read from C directly
+      // the mover's column: cached, newly cached, or (cache full, or a helper's prefetch
+      // of it still in flight) read from C directly. Loads past the row's ldc = T * 64
+      // entries are clamped to its last set, not predicated (eight lane masks held across
+      // the walk are SGPRs this function does not have): they only reach the gradients of
+      // the sets >= T, which no pass visits or stores.
       float cv[8];
-      if (slj < 0 && ncache < S_CAP) {
 #ifdef ENET_PROF
-        ++nfetch_;
+      int own_ = slj < 0;   // the column comes from C: read by wave 0 itself
 #endif
-        slj = ncache++;
-        const float* Cj = Cf + (int64_t)j * ldc;
+      if (slj < 0) {
+        // a helper wave may have cached the column since this pass read sslot: one LDS
+        // round trip, on the moves of a coordinate without a slot only
+        slj = __builtin_amdgcn_readfirstlane(__hip_atomic_load(
+            sslot + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (slj >= 0 && lane == lj) slS[SJ] = slj;
+#ifdef ENET_PROF
+        own_ = slj < 0;
+#endif
+      }
+      // no slot and no prefetch in flight: take one while the cache has room
+      int got;
+      if (slj == SLOT_NONE && (got = enet_take_slot_w0(sncache)) < S_CAP) {
+        slj = got;
+        const float* Cj = Cf + j * ldc;   // j * ldc <= PMAX * PMAX
         LDS_AS float* dst = sccache + slj * PMAX;
 #pragma unroll
         for (int s8 = 0; s8 < 8; ++s8) {
           const int k = s8 * 64 + lane;
-          const float v = k < ldc ? Cj[k] : 0.f;
+          const float v = Cj[min(s8, T - 1) * 64 + lane];
           cv[s8] = v;
           dst[(s8 >> 2) * 256 + lane * 4 + (s8 & 3)] = v;
         }
-        if (lane == 0) sslot[j] = slj;
+        // (no release: only wave 0 reads the cache, the helpers only test the slot)
+        if (lane == 0)
+          __hip_atomic_store(sslot + j, slj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (lane == lj) slS[SJ] = slj;
+#ifdef ENET_PROF
+        own_ = 1;
+#endif
       } else if (slj >= 0) {
         const LDS_AS float* src = sccache + slj * PMAX + lane * 4;
 #pragma unroll
@@ -578,15 +738,23 @@ __device__ __noinline__ PassS enet_pass_s(bool full, int T, int ldc, double ab, 
           cv[4 + e] = src[256 + e];
         }
       } else {
-        const float* Cj = Cf + (int64_t)j * ldc;
+        // the speculative share (S_SPEC) keeps a slot free for every mover below the
+        // mode-switch point
+        ATE_DASSERT(slj == SLOT_FLIGHT || ever_n > ENET_S_ENTER);
+        const float* Cj = Cf + j * ldc;   // j * ldc <= PMAX * PMAX
 #pragma unroll
-        for (int s8 = 0; s8 < 8; ++s8) cv[s8] = s8 * 64 + lane < ldc ? Cj[s8 * 64 + lane] : 0.f;
+        for (int s8 = 0; s8 < 8; ++s8) cv[s8] = Cj[min(s8, T - 1) * 64 + lane];
       }
 #pragma unroll
       for (int s8 = 0; s8 < 8; ++s8) gS[s8] = __builtin_fma(-(double)cv[s8], d, gS[s8]);
       // bookkeeping of j (glmnet: the gradient BEFORE the move enters rsq)
       const int evj = __builtin_amdgcn_readlane(flb, lj);
-      if (!((evj >> (8 + SJ)) & 1)) ++ever_n;
+      if (!((evj >> (8 + SJ)) & 1)) {   // j's first move
+        ++ever_n;
+#ifdef ENET_PROF
+        if (own_) ++nfetch_; else ++nused_;
+#endif
+      }
       if (lane == lj) {
         flb |= 1 << (8 + SJ);
         aS[SJ] = an;
@@ -607,16 +775,15 @@ __device__ __noinline__ PassS enet_pass_s(bool full, int T, int ldc, double ab, 
       if ((flb >> (8 + s8)) & 1) sflag[k] |= 2;
     }
   }
-  if (lane == 0) {
-    *sever_n = ever_n;
-    *sncache = ncache;
-  }
+  if (lane == 0) *sever_n = ever_n;
 #ifdef ENET_PROF
-  if (lane == 0) {   // mode S: [19] passes, [20] candidates visited, [21] cycles, [22] fetches
+  if (lane == 0) {   // mode S: [19] passes, [20] candidates visited, [21] cycles, [22] first
+                     // moves whose column wave 0 read from C itself
     sprof_row[19] += 1ull;
     sprof_row[20] += nit_;
     sprof_row[21] += (unsigned long long)(clock64() - tps0_);
     sprof_row[22] += nfetch_;
+    sprof_row[33] += nused_;   // [33] first moves that found a helper's prefetched column
   }
 #endif
   return PassS{dlx, rsq_add};
@@ -643,7 +810,7 @@ __global__ __launch_bounds__(NTH) void enet_path_kernel(
     double alpha, double flmin, double thr, int maxit,
     double* __restrict__ apath, double* __restrict__ lams, double* __restrict__ rsqs,
     int* __restrict__ nlam_out, int* __restrict__ npass_out, int L, int* __restrict__ progress,
-    long spin_max, double* __restrict__ lampub) {
+    long spin_max, double* __restrict__ lampub, int s_prefetch) {
   constexpr int TMAX = PMAX / 64;
   __shared__ double sg[PMAX], sa[PMAX], svp[PMAX], sdc[PMAX];
   // Mode L's snapshots and staged blocks share one LDS region with mode S's column cache
@@ -658,12 +825,12 @@ __global__ __launch_bounds__(NTH) void enet_path_kernel(
   float* const sccache = reinterpret_cast<float*>(s_union);
   __shared__ int sslot[PMAX];             // mode S: cache slot of coordinate k (-1: none)
   __shared__ int sever_n;                 // mode S: coordinates that have ever moved
-  __shared__ int sncache;                 // mode S: cached columns
+  __shared__ int sncache;                 // mode S: cache slots handed out
   // phase-B hand-offs without a second barrier: wave 0's publication count (visits whose
   // block t it has published) and the pull waves' phase-B arrival count (NP per visit
   // with a prefetch block)
   __shared__ int spub, sarr;
-  __shared__ int sfetch0;                 // mode S: cached columns at the lambda's start
+  __shared__ int sfetch0;                 // mode S: movers' columns at the lambda's start
   __shared__ int sflag[PMAX];             // bit0 ju, bit1 active
   __shared__ double spart2[2][NW][64];    // pull partials (and fp64 own-delta corr, slot 0),
                                           // double-buffered by visit parity
@@ -676,8 +843,8 @@ __global__ __launch_bounds__(NTH) void enet_path_kernel(
   // per-wave cycle accumulators in LDS (lane 0 of a wave adds to its own row), flushed to
   // enet_prof once at kernel end: no global atomics (and their vmcnt waits at barriers)
   // inside the visit loop
-  __shared__ unsigned long long sprof[NW][32];
-  for (int e = threadIdx.x; e < NW * 32; e += blockDim.x) (&sprof[0][0])[e] = 0ull;
+  __shared__ unsigned long long sprof[NW][PROF_N];
+  for (int e = threadIdx.x; e < NW * PROF_N; e += blockDim.x) (&sprof[0][0])[e] = 0ull;
 #endif
   __shared__ __attribute__((aligned(16))) CT sdelta[PMAX];
   __shared__ int slist[PMAX];             // compacted pending columns (per-wave quarters)
@@ -731,6 +898,9 @@ __global__ __launch_bounds__(NTH) void enet_path_kernel(
   __syncthreads();
   const int nlam = pr.ulam_src >= 0 ? L : pr.nlam_req;
   const double alf = pr.ulam_src >= 0 ? 1.0 : pow(flmin, 1.0 / (double)(nlam - 1));
+  // the path's lambda ratio, for a fold problem too (its source's): the mode-S prefetch
+  // looks one lambda ahead with it (a heuristic: speed only)
+  const double lam_ratio = pr.ulam_src < 0 ? alf : L > 1 ? pow(flmin, 1.0 / (double)(L - 1)) : 1.0;
   double alm = 0.0, rsq = 0.0, rsq_prev = 0.0;
   int npass = 0, m_out = 0;
   double ab = 0.0, dem = 0.0;
@@ -1026,6 +1196,18 @@ __global__ __launch_bounds__(NTH) void enet_path_kernel(
           sdl = r.dlx;
           rsq_l += r.rsq;
         }
+      } else if (s_prefetch) {
+        enet_prefetch_s(wid - 1, T, ldc, ab * lam_ratio, reinterpret_cast<const float*>(Cq),
+                        (const LDS_AS double*)sg, (const LDS_AS double*)sa,
+                        (const LDS_AS double*)svp, (const LDS_AS int*)sflag, (LDS_AS int*)sslot,
+                        (LDS_AS float*)sccache, (const LDS_AS int*)&sever_n,
+                        (LDS_AS int*)&sncache,
+#ifdef ENET_PROF
+                        (LDS_AS unsigned long long*)&sprof[wid][0]
+#else
+                        nullptr
+#endif
+        );
       }
       __syncthreads();
       const double r = sdl;
@@ -1577,9 +1759,12 @@ __global__ __launch_bounds__(NTH) void enet_path_kernel(
     dem = LASSO ? 0.0 : alm * (1.0 - alpha);
     // leave mode S for good once many coordinates have moved or the last lambda fetched
     // many new columns (cheap in mode L, where a new mover's row is pulled by the helpers)
-    const int fetched = sncache - sfetch0;
+    // (the movers' columns, min(sever_n, S_CAP): every first move takes a slot while one is
+    // free; not the slots handed out, which include the helper waves' prefetches)
+    const int evc = min(sever_n, S_CAP);
+    const int fetched = evc - sfetch0;
     __syncthreads();
-    if (tid == 0) sfetch0 = sncache;
+    if (tid == 0) sfetch0 = evc;
     if (modeS && (sever_n > ENET_S_ENTER || fetched > ENET_S_FETCH)) {
       // to mode L for the rest of the path: every gradient is exact (Dcum = 0), so the
       // snapshots the column cache overwrote restart at zero and every block is pulled anew
@@ -1666,7 +1851,7 @@ __global__ __launch_bounds__(NTH) void enet_path_kernel(
   }
 #ifdef ENET_PROF
   __syncthreads();
-  if (tid < 32) {
+  if (tid < PROF_N) {
     unsigned long long acc = 0;
     for (int w = 0; w < NW; ++w) acc += sprof[w][tid];
     // [10] / [11]: shader clock cycles and 100 MHz wall ticks of the whole path (clock rate)
@@ -1687,7 +1872,7 @@ extern "C" __attribute__((visibility("default"))) int ate_enet_prof_read(void* h
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(enet_prof), sizeof(enet_prof));
 }
 extern "C" __attribute__((visibility("default"))) int ate_enet_prof_reset() {
-  static unsigned long long z[256][32];
+  static unsigned long long z[256][PROF_N];
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(enet_prof), z, sizeof(z));
 }
 #endif
@@ -1711,12 +1896,15 @@ ATE_API int ate_enet_path(const void* C, int c_f32, const void* g, int p, int ny
   // ATE_ENET_SPIN_MAX overrides it (tests force the timeout path with 0)
   const char* sm = getenv("ATE_ENET_SPIN_MAX");
   const long spin_max = sm ? atol(sm) : (1l << 26);
+  // ATE_ENET_S_PREFETCH=0: mode S without the helper waves' column prefetch (same results)
+  const char* sp = getenv("ATE_ENET_S_PREFETCH");
+  const int s_prefetch = sp ? atoi(sp) != 0 : 1;
 #define LAUNCH_C(CTT, LS)                                                                      \
   ATE_LAUNCH((enet_path_kernel<CTT, LS>), dim3(nwg), dim3(NTH), 0, s, (const CTT*)C,   \
                      (const double*)g, p, ny, (const unsigned char*)ju, (const double*)ys,     \
                      (const double*)vp, (const EnetProblem*)probs, nprob, alpha, flmin, thr,   \
                      maxit, (double*)apath, (double*)lams, (double*)rsqs, (int*)nlam_out,     \
-                     (int*)npass_out, L, (int*)progress, spin_max, (double*)lampub)
+                     (int*)npass_out, L, (int*)progress, spin_max, (double*)lampub, s_prefetch)
   const bool lasso = alpha == 1.0;
   if (c_f32 && lasso) LAUNCH_C(float, true);
   else if (c_f32) LAUNCH_C(float, false);

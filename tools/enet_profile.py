@@ -15,6 +15,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 LIB = ROOT / "ate_replication_causalml_amd" / "_lib" / "libatehip_prof.so"
+NCOL = 40   # PROF_N of csrc/enet.hip
 
 
 def build():
@@ -51,13 +52,13 @@ def run(n, p):
     _, _, cv = dml_crossfit_panel(pan, 5, "min")
     t[1].record()
     torch.cuda.synchronize()
-    buf = np.zeros((256, 32), dtype=np.uint64)
+    buf = np.zeros((256, NCOL), dtype=np.uint64)
     lib.ate_enet_prof_read(buf.ctypes.data_as(ctypes.c_void_p))
     rows = buf[:40]
     live = rows[rows[:, 3] > 0]
     print(json.dumps({"step_ms": t[0].elapsed_time(t[1]),
-                      "per_problem": [[int(v) for v in r[:32]] for r in live],
-                      "note": "[0] phase B + pass-start pulls, [1] phase A, [2] wave-0 phase A, [3] visits, [4] wave-1 phase A, [5] wall ticks inside passes, [6] wave-0 loop ticks, [7] updates, [8] pass-start pulls, [9] wave-0 phase B, [10] shader cycles, [11] wall ticks (100 MHz), [12] mode-L passes with visits, [13] empty passes, [14] wave-0 visits, [15] loop-only cycles, [16] wave-1 phase B, [17] prologue cycles, [18] last pull wave phase A, [19]-[22] mode S passes / candidates / cycles / fetches, [23] mode-S loop cycles, [24] prologue before the arrival wait, [25] the wait, [26] after the wait, [27] wave-0 phase-A barrier, [28] post-walk cycles"}))
+                      "per_problem": [[int(v) for v in r[:NCOL]] for r in live],
+                      "note": "[0] phase B + pass-start pulls, [1] phase A, [2] wave-0 phase A, [3] visits, [4] wave-1 phase A, [5] wall ticks inside passes, [6] wave-0 loop ticks, [7] updates, [8] pass-start pulls, [9] wave-0 phase B, [10] shader cycles, [11] wall ticks (100 MHz), [12] mode-L passes with visits, [13] empty passes, [14] wave-0 visits, [15] loop-only cycles, [16] wave-1 phase B, [17] prologue cycles, [18] last pull wave phase A, [19]-[21] mode S passes / candidates / cycles, [22] first moves whose column wave 0 read from C itself (into a cache slot, or directly with the cache full or a prefetch in flight), [23] mode-S loop cycles, [24] prologue before the arrival wait, [25] the wait, [26] after the wait, [27] wave-0 phase-A barrier, [28] post-walk cycles, [29] lambda start -> first pass (wall ticks), [30] last pass -> lambda end (wall ticks), [32] columns prefetched by the helper waves, [33] first moves that found their column prefetched (ATE_ENET_S_PREFETCH=0: both 0)"}))
 
 
 if __name__ == "__main__":
