@@ -107,6 +107,7 @@ _SIGS = {
     "ate_irm_target_moments": "ipllpipiipiiiiidippp",
     "ate_irm_score_link": "ii" + "ipllpipiipiiiiidippp",
     "ate_iivm_moments": "ipllpipiipiiiiiiidippp",
+    "ate_apo_moments": "ipllpipiipiiiiidippp",
     "ate_group_boot": "pppliiuippp",
     "ate_group_boot_scratch": "iii",
     "ate_cate_moments": "ppplpiiippp",

@@ -27,7 +27,10 @@ its sensitivity to unobserved confounding (DoubleML sensitivity_analysis /
 sensitivity_benchmark) -> ate_dml_irm_sensitivity;
 its effect on the treated and on the controls with the joint covariance (DoubleML
 IRM(score="ATTE"), grf average_treatment_effect(target.sample=)) -> ate_dml_irm_targets;
-the LATE with a binary instrument under noncompliance (DoubleML DoubleMLIIVM) -> ate_dml_iivm.
+the LATE with a binary instrument under noncompliance (DoubleML DoubleMLIIVM) -> ate_dml_iivm;
+the mean potential outcomes of a multi-valued treatment, their contrasts against a reference
+level and a simultaneous band (DoubleML DoubleMLAPOS / causal_contrast, grf
+multi_arm_causal_forest) -> ate_dml_apos.
 """
 from __future__ import annotations
 
@@ -37,7 +40,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import (AteResult, CateResult, GateResult, LateResult, PolicyTreeResult, SensitivityResult,
+from .result import (ApoResult, AteResult, CateResult, GateResult, LateResult, PolicyTreeResult, SensitivityResult,
                      TargetResult, format_table, results_frame)
 from .utils import guards
 from .utils.tracing import trace
@@ -432,6 +435,32 @@ def ate_dml_iivm(Y, W, Z, X, folds=5, lambda_rule="min", clip=0.01, always_taker
                                  never_takers=never_takers, device=run.device(), dtype=run.dtype)
 
 
+def ate_dml_apos(Y, D, X, reference=None, folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                 n_boot=999, level=0.95, run=None, repeats=1, propensity="linear") -> ApoResult:
+    """The mean potential outcomes of a treatment D with 2 to 8 distinct values under the
+    cross-fitted interactive model (DoubleML DoubleMLAPOS, grf multi_arm_causal_forest) with
+    CV-LASSO nuisances: per level c the outcome regression on the rows of that level and the
+    one-vs-rest linear-probability propensity of 1{D = c}, clipped to [clip, 1 - clip]
+    (estimators/apos.py). The result carries every level's mean with the joint covariance,
+    ``result.contrasts(reference=)`` -- every level's effect against ``reference`` (a value of
+    D; default the lowest) with pointwise bounds and a simultaneous ``level`` band from
+    ``n_boot`` Gaussian draws -- and ``result.wald()``, the test that all means are equal.
+    ``seed`` keys the folds and the band; ``run`` picks the backend, device and panel type.
+    Repeated cross-fitting (``repeats`` other than 1), ``propensity="logit"`` and group, curve,
+    policy and sensitivity versions are not available (ValueError)."""
+    run = _run(run)
+    with trace("ate_dml_apos", folds=folds):
+        from .estimators import apos as DA
+        DA.check_scope(repeats, propensity)
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_apos_lasso(Y, D, X, reference=reference, folds=folds, seed=seed,
+                                    lambda_rule=lambda_rule, clip=clip, n_boot=n_boot, level=level)
+        return DA.dml_apos_lasso(Y, D, X, reference=reference, folds=folds, seed=seed,
+                                 lambda_rule=lambda_rule, clip=clip, n_boot=n_boot, level=level,
+                                 device=run.device(), dtype=run.dtype)
+
+
 def ate_residual_balance(Y, W, X, balance: BalanceConfig | None = None,
                          method="residual_balancing", run=None) -> AteResult:
     """E14 residual_balance_ATE (ate_functions.R:393-405) -> balanceHD::residualBalance.ate."""
@@ -605,7 +634,7 @@ def replicate(data=None, config: ReplicateConfig | None = None, log_path=None, p
 __all__ = [
     "ate_naive", "ate_ols", "propensity_logistic", "propensity_lasso", "ate_ipw", "ate_ipw_wls",
     "ate_lasso_single", "ate_lasso", "ate_aipw_rf", "ate_aipw_glm", "ate_belloni",
-    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_policy", "ate_dml_irm_sensitivity", "ate_dml_irm_targets", "ate_dml_iivm", "ate_residual_balance", "ate_causal_forest", "replicate",
+    "ate_double_ml", "ate_dml", "ate_dml_irm", "ate_dml_irm_gate", "ate_dml_irm_cate", "ate_dml_irm_policy", "ate_dml_irm_sensitivity", "ate_dml_irm_targets", "ate_dml_iivm", "ate_dml_apos", "ate_residual_balance", "ate_causal_forest", "replicate",
     "ate_aipw_crossfit", "ate_causal_forest_bootstrap",
-    "Replication", "AteResult", "CateResult", "GateResult", "PolicyTreeResult", "SensitivityResult", "TargetResult", "LateResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
+    "Replication", "ApoResult", "AteResult", "CateResult", "GateResult", "PolicyTreeResult", "SensitivityResult", "TargetResult", "LateResult", "RunConfig", "ReplicateConfig", "BalanceConfig",
 ]

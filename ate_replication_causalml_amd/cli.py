@@ -3,6 +3,7 @@
   replicate  run the 14-row driver (ate_replication.Rmd) and print/log/plot it
   dml        K-fold DML cross-fit on a synthetic N x p panel (the north-star job)
   late       the LATE of the interactive IV model (DML-IIVM) on a synthetic encouragement design
+  apos       the mean potential outcomes of a multi-arm treatment (DML-APOS) on a synthetic mailing design
   build      compile the gfx950 HIP library and the host C++ library
 """
 from __future__ import annotations
@@ -245,6 +246,24 @@ def _late(a):
     return 0
 
 
+def _apos(a):
+    # the mean potential outcomes of every arm on the multi-arm mailing design of data.dgp
+    from .api import ate_dml_apos
+    from .config import RunConfig
+    from .data.dgp import make_multiarm_data
+    try:
+        d = make_multiarm_data(a.n, a.seed, levels=a.levels)
+        r = ate_dml_apos(d.Y, d.D, d.X, folds=a.folds, seed=a.seed, lambda_rule=a.lambda_rule,
+                         clip=a.clip, run=RunConfig(backend=a.backend, dtype=a.dtype, seed=a.seed))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    out = json.loads(r.json())
+    out["arms"] = d.arms
+    out["apo_true"] = [float(v) for v in d.apo_true]
+    print(json.dumps(out))
+    return 0
+
+
 def _build(a):
     from . import _build as b
     b.build_all()
@@ -338,6 +357,18 @@ def main(argv=None):
     l.add_argument("--backend", default="auto", choices=["auto", "gpu", "cpu", "reference"])
     l.add_argument("--dtype", default="f64", choices=["f64", "f32", "bf16"])
     l.set_defaults(fn=_late)
+    m = sub.add_parser("apos")
+    m.add_argument("--n", type=int, default=50_000)
+    m.add_argument("--levels", type=int, default=5,
+                   help="arms of the design, the control included (2..8)")
+    m.add_argument("--seed", type=int, default=1991)
+    m.add_argument("--folds", type=int, default=5)
+    m.add_argument("--clip", type=float, default=0.01,
+                   help="every arm's propensity is clipped to [clip, 1 - clip]")
+    m.add_argument("--lambda-rule", default="min", choices=["min", "1se"])
+    m.add_argument("--backend", default="auto", choices=["auto", "gpu", "cpu", "reference"])
+    m.add_argument("--dtype", default="f64", choices=["f64", "f32", "bf16"])
+    m.set_defaults(fn=_apos)
     b = sub.add_parser("build")
     b.set_defaults(fn=_build)
     a = ap.parse_args(argv)

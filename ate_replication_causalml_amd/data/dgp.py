@@ -252,3 +252,71 @@ def make_late_data(n: int = 50_000, seed: int = 1991, p_extra: int = 0, always_t
     Y = (_uniform(seed, S_YL, idx) < base + tau * D).astype(np.float64)
     return LateData(X=X, Y=Y, D=D, Z=Z, names=list(d.names), late_true=float(tau[types == 0].mean()),
                     types=types)
+
+
+S_ARM = 73          # multi-arm data: the arm assigned
+S_YM = 74           # multi-arm data: the outcome
+
+ARM_NAMES = ("control", "civic_duty", "hawthorne", "self", "neighbors")
+# the effect of each arm on P(Y = 1) at sex = 0.5: the control, then the four mailings in the
+# experiment's order (its effects grow from civic duty to neighbours), then three stronger
+# arms for designs with more than five levels
+ARM_EFFECTS = (0.0, 0.018, 0.026, 0.049, 0.081, 0.10, 0.12, 0.14)
+
+
+@dataclass
+class MultiArmData:
+    X: np.ndarray          # (n, p) float64, the tutorial's covariates
+    Y: np.ndarray          # (n,) float64 in {0,1}
+    D: np.ndarray          # (n,) float64 in {0, .., levels - 1}: the arm (0 = control)
+    names: list
+    arms: list             # the arms' names, by level
+    apo_true: np.ndarray   # (levels,) the sample mean of P(Y = 1 | X, arm c), every row in arm c
+    propensity: np.ndarray  # (n, levels) P(D = c | X)
+
+    @property
+    def n(self):
+        return self.X.shape[0]
+
+
+def make_multiarm_data(n: int = 50_000, seed: int = 1991, levels: int = 5, p_extra: int = 0,
+                       params: DgpParams = TUTORIAL) -> MultiArmData:
+    """The mailing experiment with all its arms on the tutorial's covariates
+    (``make_tutorial_data``): a control group (level 0) and ``levels - 1`` mailings (2 <=
+    levels <= 8; five is the experiment: civic duty, Hawthorne, self, neighbours), assigned
+    with probabilities that depend on X, so the naive contrasts are biased. With s = sigmoid
+    and u = 0.5 yob + 0.8 (g2000 - 0.85), yob the draw before standardisation:
+
+        P(D = c | X) = softmax_c(a_c + b_c u),  a_0 = log(levels + 3), a_c = 0 (c >= 1),
+                       b_c = 0.25 c  (the stronger the mailing, the more it goes to likely voters)
+        P(Y = 1)     = 0.2 + 0.3 s(0.8 yob + 0.5 (g2000 - 0.85)) + tau_D,
+        tau_c        = ARM_EFFECTS[c] (1 + 0.5 (sex - 0.5))
+
+    ``apo_true[c]`` is the sample mean of P(Y = 1) had every row received arm c. Every draw is
+    a Philox function of (seed, stream, row), and a row's D and Y are functions of (seed, row)
+    alone (the standardised X depends on n through its column means)."""
+    levels = int(levels)
+    if not 2 <= levels <= len(ARM_EFFECTS):
+        raise ValueError(f"levels must be in 2..{len(ARM_EFFECTS)}, got {levels}")
+    d = make_tutorial_data(n, seed, p_extra, params)
+    X = d.X
+    col = {k: X[:, j] for j, k in enumerate(d.names)}
+    s = lambda v: 1.0 / (1.0 + np.exp(-v))
+    idx = np.arange(n, dtype=np.uint64)
+    yob = _normal(seed, S_CTS + 0, idx)     # the unscaled draw: D and Y do not depend on n
+    u = 0.5 * yob + 0.8 * (col["g2000"] - 0.85)
+    score = np.stack([(np.log(levels + 3.0) if c == 0 else 0.0) + 0.25 * c * u
+                      for c in range(levels)], axis=1)
+    score -= score.max(axis=1, keepdims=True)
+    prob = np.exp(score)
+    prob /= prob.sum(axis=1, keepdims=True)
+    cum = np.cumsum(prob, axis=1)
+    cum[:, -1] = 1.0
+    D = (_uniform(seed, S_ARM, idx)[:, None] >= cum).sum(axis=1).astype(np.float64)
+    base = 0.2 + 0.3 * s(0.8 * yob + 0.5 * (col["g2000"] - 0.85))
+    tau = np.asarray(ARM_EFFECTS[:levels])[None, :] * (1.0 + 0.5 * (col["sex"] - 0.5))[:, None]
+    p_all = base[:, None] + tau
+    Y = (_uniform(seed, S_YM, idx) < p_all[np.arange(n), D.astype(np.int64)]).astype(np.float64)
+    arms = [ARM_NAMES[c] if c < len(ARM_NAMES) else f"arm{c}" for c in range(levels)]
+    return MultiArmData(X=X, Y=Y, D=D, names=list(d.names), arms=arms,
+                        apo_true=p_all.mean(axis=0), propensity=prob)

@@ -32,6 +32,8 @@ P_SUBSAMPLE = 6     # grf half-sampling / honesty split
 P_GBDT = 7          # GBDT row/feature subsampling
 P_SAMPLE_ROWS = 8   # sample_n row selection in the data pipeline
 P_MULT = 9          # Rademacher multipliers of the grouped multiplier bootstrap (csrc/gate.hip)
+P_BAND = 10         # normals of the simultaneous band over contrasts (result.ApoResult; drawn
+                    # on the host only, so it has no device twin)
 
 
 def philox4x32(c0, c1, c2, c3, k0, k1, rounds: int = 10):

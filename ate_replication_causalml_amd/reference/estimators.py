@@ -962,6 +962,75 @@ def dml_iivm_lasso(Y, W, Z, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
     return LateResult.from_moments(method, mom, n=n, hipgraph=False)
 
 
+def _apos_scores(Y, D, X, folds, seed, lambda_rule, clip, fold_ids=None):
+    """The held-out nuisances and the per-row potential-outcome scores of a multi-valued
+    treatment (validated inputs as float64 arrays), in the shape of _irm_scores: (psi [n, L],
+    values [L], level [n], g [n, L], m [n, L]), m before clipping. g_c is fitted on the
+    training rows with D = values[c], m_c on all training rows with the target 1{D = c}."""
+    if not np.isfinite(D).all():
+        raise ValueError("DML-APOS needs a finite treatment: D has NaN or infinite values")
+    values, level = np.unique(D, return_inverse=True)
+    level = level.reshape(-1)
+    L = len(values)
+    if not 2 <= L <= 8:
+        raise ValueError(f"DML-APOS needs between 2 and 8 treatment levels, D has {L} distinct "
+                         f"value{'' if L == 1 else 's'}")
+    fid = rng.fold_ids(len(Y), folds, seed, stream=0) if fold_ids is None else \
+        np.asarray(fold_ids, dtype=np.int64)
+    for k in range(folds):
+        for c in range(L):
+            if not np.any((fid == k) & (level == c)):
+                raise ValueError(f"empty (fold, level) cell: fold {k}, level D={values[c]:g} has "
+                                 "no rows")
+    s = "lambda.min" if lambda_rule == "min" else "lambda.1se"
+    n = len(Y)
+    g, m = np.empty((n, L)), np.empty((n, L))
+    for k in range(folds):
+        te = fid == k
+        inner = np.where(fid > k, fid - 1, fid)
+        for c in range(L):
+            rows = (~te) & (level == c)
+            cv = gn.cv_glmnet(X[rows], Y[rows], foldid=inner[rows])
+            g[te, c] = cv.predict(X[te], s=s)
+            cv = gn.cv_glmnet(X[~te], (level[~te] == c).astype(np.float64), foldid=inner[~te])
+            m[te, c] = cv.predict(X[te], s=s)
+    own = np.arange(n)
+    e = np.clip(m[own, level], clip, 1 - clip)
+    psi = g.copy()
+    psi[own, level] += (Y - g[own, level]) / e
+    return psi, values, level, g, m
+
+
+def dml_apos_lasso(Y, D, X, reference=None, folds=5, seed=1991, lambda_rule="min", clip=0.01,
+                   n_boot=999, level=0.95, method="DML-APOS cross-fit (LASSO)", fold_ids=None,
+                   keep_scores=False):
+    """The mean potential outcomes of a treatment with 2 to 8 distinct values under the
+    cross-fitted interactive model (DoubleML DoubleMLAPOS) with CV-LASSO nuisances, row by row
+    in float64, the twin of estimators.apos.dml_apos_lasso: psi_c = g_c + 1{D = c}(Y - g_c) /
+    clip(m_c), theta = the column means of psi [n, L], Cov = phi' phi / (n - 1) / n with phi
+    the centred scores. The per-level diagnostics are taken over the per-row arrays here;
+    ``keep_scores`` leaves psi in the result's ``scores``."""
+    from ..result import ApoResult
+    Y, D, X = _arr(Y), _arr(D), _arr(X)
+    psi, values, lev, g, m = _apos_scores(Y, D, X, folds, seed, lambda_rule, clip, fold_ids)
+    n, L = psi.shape
+    own = np.arange(n)
+    m_own, g_own = m[own, lev], g[own, lev]
+    out = (m_own < clip) | (m_own > 1 - clip)
+    e = np.clip(m_own, clip, 1 - clip)
+    n_c = np.bincount(lev, minlength=L)
+    res = ApoResult.from_scores(
+        method, psi, [float(v) for v in values], reference=reference, seed=seed, n_boot=n_boot,
+        level=level, n=n, hipgraph=False, n_c=[int(v) for v in n_c],
+        n_clipped_c=[int(v) for v in np.bincount(lev, weights=out, minlength=L)],
+        rmse_g_c=[float(v) for v in np.sqrt(np.bincount(lev, weights=(Y - g_own) ** 2,
+                                                        minlength=L) / n_c)],
+        ipw_c=[float(v) for v in np.bincount(lev, weights=1.0 / e, minlength=L) / n])
+    if keep_scores:
+        res.scores = psi
+    return res
+
+
 def dml_plr_lasso_repeated(Y, W, X, folds=5, repeats=3, seed=1991, lambda_rule="min",
                            aggregate="median", method="DML cross-fit (LASSO, repeated)"):
     """Repeated cross-fitting (Chernozhukov et al. 2018 §3.4, median method): S = repeats

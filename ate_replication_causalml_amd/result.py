@@ -936,6 +936,357 @@ class LateResult:
     to_json = json
 
 
+# ------------------------------------------- potential outcomes of a multi-valued treatment
+APO_MIN_LEVELS, APO_MAX_LEVELS = 2, 8
+APO_LEVEL_MOMENTS = ("n_c", "n_clipped_c", "S 1{D=c}(y-g_c)^2", "S 1{D=c}/e_c")
+
+
+@dataclass(frozen=True)
+class ApoLayout:
+    """Where the moments of the potential-outcome pass live for L levels (the host twin of
+    csrc/apo.hip ``apo_n`` and its header): ``n`` at 0, ``S psi_c`` at ``psi + c``,
+    ``S psi_c psi_c'`` (c <= c') at ``tri(c, c')``, and per level c the four sums of
+    APO_LEVEL_MOMENTS at ``level + 4 c + q``. ``size``: 14 at L = 2, 77 at L = 8."""
+    L: int
+
+    def __post_init__(self):
+        if not APO_MIN_LEVELS <= self.L <= APO_MAX_LEVELS:
+            raise ValueError(f"the potential-outcome pass takes {APO_MIN_LEVELS} to "
+                             f"{APO_MAX_LEVELS} treatment levels, got {self.L}")
+
+    @property
+    def psi(self) -> int:
+        return 1
+
+    @property
+    def cross(self) -> int:
+        return 1 + self.L
+
+    @property
+    def level(self) -> int:
+        return 1 + self.L + self.L * (self.L + 1) // 2
+
+    @property
+    def size(self) -> int:
+        return self.level + 4 * self.L
+
+    def tri(self, c: int, c2: int) -> int:
+        """The index of S psi_c psi_c2: row-major over the upper triangle."""
+        c, c2 = (c, c2) if c <= c2 else (c2, c)
+        return self.cross + c * self.L - c * (c - 1) // 2 + (c2 - c)
+
+    def names(self) -> list:
+        L = self.L
+        return (["n"] + [f"S psi_{c}" for c in range(L)] +
+                [f"S psi_{c} psi_{d}" for c in range(L) for d in range(c, L)] +
+                [m for c in range(L) for m in (f"n_{c}", f"n_clipped_{c}",
+                                               f"S 1{{D={c}}}(y-g_{c})^2", f"S 1{{D={c}}}/e_{c}")])
+
+
+def apo_layout(L: int) -> ApoLayout:
+    return ApoLayout(int(L))
+
+
+def apo_levels_of(n_moments: int) -> int:
+    """L from the length of a moment vector."""
+    for L in range(APO_MIN_LEVELS, APO_MAX_LEVELS + 1):
+        if ApoLayout(L).size == n_moments:
+            return L
+    raise ValueError(f"{n_moments} is not the moment count of any number of levels in "
+                     f"{APO_MIN_LEVELS}..{APO_MAX_LEVELS}")
+
+
+def apo_estimates(mom):
+    """(theta [L], cov [L][L]) from the moments, float64 on the host: theta_c = S psi_c / n and
+    cov_cc' = (S psi_c psi_c' - S psi_c S psi_c' / n) / (n - 1) / n, the n - 1 rule of
+    ``irm.mean_se`` (its square on the diagonal)."""
+    m = [float(v) for v in mom]
+    lay = ApoLayout(apo_levels_of(len(m)))
+    L, n = lay.L, m[0]
+    nan = float("nan")
+    head = m[:lay.level]
+    if not (math.isfinite(n) and n > 1 and all(math.isfinite(v) for v in head)):
+        return [nan] * L, [[nan] * L for _ in range(L)]
+    s = m[lay.psi:lay.psi + L]
+    cov = [[(m[lay.tri(c, d)] - s[c] * s[d] / n) / (n - 1) / n for d in range(L)] for c in range(L)]
+    return [v / n for v in s], cov
+
+
+def _chol_psd(A):
+    """The lower Cholesky factor of a symmetric positive semidefinite matrix (lists), with a
+    zero column where a pivot is not positive (a degenerate direction draws nothing)."""
+    k = len(A)
+    Lc = [[0.0] * k for _ in range(k)]
+    for j in range(k):
+        d = A[j][j] - sum(Lc[j][q] ** 2 for q in range(j))
+        if not d > 1e-14 * max(abs(A[j][j]), 1e-300):
+            continue
+        Lc[j][j] = math.sqrt(d)
+        for i in range(j + 1, k):
+            Lc[i][j] = (A[i][j] - sum(Lc[i][q] * Lc[j][q] for q in range(j))) / Lc[j][j]
+    return Lc
+
+
+def _chi2_sf(x: float, df: int) -> float:
+    """P(chi2_df > x): the regularised upper incomplete gamma function Q(df / 2, x / 2), by
+    its series below a + 1 and its continued fraction above (Numerical Recipes 6.2)."""
+    if not (x == x) or df < 1:
+        return float("nan")
+    if x <= 0.0:
+        return 1.0
+    a, x = df / 2.0, x / 2.0
+    lg = math.lgamma(a)
+    if x < a + 1.0:
+        term = tot = 1.0 / a
+        for k in range(1, 10000):
+            term *= x / (a + k)
+            tot += term
+            if abs(term) < abs(tot) * 1e-16:
+                break
+        return max(0.0, 1.0 - tot * math.exp(-x + a * math.log(x) - lg))
+    tiny = 1e-300
+    b = x + 1.0 - a
+    c, d = 1.0 / tiny, 1.0 / b
+    h = d
+    for k in range(1, 10000):
+        an = -k * (k - a)
+        b += 2.0
+        d = an * d + b
+        d = tiny if abs(d) < tiny else d
+        c = b + an / c
+        c = tiny if abs(c) < tiny else c
+        d = 1.0 / d
+        h *= d * c
+        if abs(d * c - 1.0) < 1e-16:
+            break
+    return h * math.exp(-x + a * math.log(x) - lg)
+
+
+def contrast_cov(cov, r: int):
+    """The covariance [L-1][L-1] of the contrasts theta_c - theta_r, c != r in ascending
+    order: V_cd + V_rr - V_cr - V_dr."""
+    idx = [c for c in range(len(cov)) if c != r]
+    return [[cov[c][d] + cov[r][r] - cov[c][r] - cov[d][r] for d in idx] for c in idx]
+
+
+def band_crit(ccov, seed: int, level: float = 0.95, n_boot: int = 999) -> float:
+    """The critical value of a simultaneous ``level`` band over contrasts with covariance
+    ``ccov``. The maximal |t| of a Gaussian multiplier bootstrap of the scores is, given the
+    data, exactly max |N(0, R)| with R the contrasts' correlation matrix, so the value is the
+    ``boot_rank(level, n_boot)``-th smallest of n_boot such maxima: draw b is ``chol(R) z_b``
+    with z_b[j] the first Box-Muller normal of Philox (seed, P_BAND, stream j, index b). A pure
+    function of (ccov, seed, level, n_boot). One contrast: the two-sided normal quantile, no
+    draws. A contrast of zero variance takes no part."""
+    rank = boot_rank(level, int(n_boot))
+    k = len(ccov)
+    if any(not (v == v) for row in ccov for v in row):
+        return float("nan")
+    if k <= 1:
+        return normal_quantile(0.5 + level / 2.0)
+    import numpy as np
+    from .parallel import rng
+    sd = [math.sqrt(ccov[j][j]) if ccov[j][j] > 0.0 else 0.0 for j in range(k)]
+    R = [[ccov[i][j] / (sd[i] * sd[j]) if sd[i] > 0 and sd[j] > 0 else 0.0 for j in range(k)]
+         for i in range(k)]
+    A = np.asarray(_chol_psd(R), dtype=np.float64)
+    b = np.arange(int(n_boot), dtype=np.uint64)
+    z = np.stack([rng.normal_pair(int(seed), rng.P_BAND, j, b)[0] for j in range(k)])   # [k, B]
+    tmax = np.abs(A @ z).max(axis=0)
+    return float(np.sort(tmax)[rank - 1])
+
+
+@dataclass
+class ApoContrast:
+    """theta_level - theta_reference with its SE from the joint covariance, the pointwise
+    1.96 SE bounds and the simultaneous bounds over all contrasts against that reference."""
+    level: object
+    reference: object
+    effect: float
+    se: float
+    lower_ci: float
+    upper_ci: float
+    lower_joint: float
+    upper_joint: float
+
+
+@dataclass
+class WaldTest:
+    stat: float
+    df: int
+    p_value: float
+
+
+@dataclass
+class ApoResult:
+    """The mean potential outcomes of a multi-valued treatment under the cross-fitted
+    interactive model (DoubleML ``DoubleMLAPOS``): ``apo[c]`` the mean outcome had everybody
+    received level ``levels[c]``, ``cov`` their joint covariance, :meth:`contrasts` every
+    level's effect against a reference with a simultaneous band (``crit``: its critical
+    value for ``reference``), :meth:`wald` the test that all means are equal. Everything is
+    a function of ``moments`` (:class:`ApoLayout`), ``seed`` and ``level``."""
+    method: str
+    levels: list                   # the original treatment values, ascending
+    reference: object              # one of ``levels``
+    apo: list                      # L AteResult
+    cov: list                      # [L][L]
+    moments: list
+    crit: float
+    n_boot: int
+    level: float
+    seed: int
+    diagnostics: dict = field(default_factory=dict)
+    scores: object = None          # keep_scores (the row-by-row reference): psi [n, L]
+
+    @classmethod
+    def from_moments(cls, method, mom, levels, reference=None, seed=1991, n_boot=999,
+                     level=0.95, **diag):
+        """From the moment vector; the per-level diagnostics (n_c, n_clipped_c, rmse_g_c,
+        ipw_c = S 1{D=c}/e_c / n, near 1 for a calibrated propensity) come from it too,
+        ``diag`` adds n and hipgraph."""
+        mom = [float(v) for v in mom]
+        levels = [v.item() if hasattr(v, "item") else v for v in levels]
+        lay = ApoLayout(len(levels))
+        if len(mom) != lay.size:
+            raise ValueError(f"{lay.size} moments expected for {lay.L} levels, got {len(mom)}")
+        reference = levels[0] if reference is None else reference
+        if reference not in levels:
+            raise ValueError(f"reference {reference!r} is not a treatment level: {levels}")
+        reference = levels[levels.index(reference)]
+        theta, cov = apo_estimates(mom)
+        return cls._build(method, levels, reference, theta, cov, mom, seed, n_boot, level,
+                          cls._level_diag(mom, lay), diag)
+
+    @classmethod
+    def from_scores(cls, method, psi, levels, reference=None, seed=1991, n_boot=999, level=0.95,
+                    **diag):
+        """From the per-row scores psi [n][L] (the row-by-row reference): the means and the
+        covariance ``phi.T @ phi / (n - 1) / n`` of the centred scores."""
+        import numpy as np
+        psi = np.asarray(psi, dtype=np.float64)
+        n = len(psi)
+        levels = [v.item() if hasattr(v, "item") else v for v in levels]
+        reference = levels[0] if reference is None else reference
+        if reference not in levels:
+            raise ValueError(f"reference {reference!r} is not a treatment level: {levels}")
+        theta = psi.mean(0)
+        phi = psi - theta
+        cov = (phi.T @ phi / (n - 1) / n).tolist()
+        return cls._build(method, levels, levels[levels.index(reference)], theta.tolist(), cov,
+                          [], seed, n_boot, level, {}, diag)
+
+    @classmethod
+    def _build(cls, method, levels, reference, theta, cov, mom, seed, n_boot, level, ldiag, diag):
+        nan = float("nan")
+        apo = []
+        for c, t in enumerate(theta):
+            se = math.sqrt(cov[c][c]) if cov[c][c] >= 0.0 else nan
+            apo.append(AteResult(f"{method}: Y({levels[c]})", t, se, t - Z * se, t + Z * se))
+        crit = band_crit(contrast_cov(cov, levels.index(reference)), seed, level, n_boot)
+        d = dict(ldiag)
+        d.update(diag)
+        if mom:
+            d.setdefault("n", int(round(mom[0])) if math.isfinite(mom[0]) else -1)
+        return cls(method, levels, reference, apo, cov, mom, crit, int(n_boot), float(level),
+                   int(seed), d)
+
+    @staticmethod
+    def _level_diag(mom, lay):
+        cnt = lambda x: int(round(x)) if math.isfinite(x) else -1
+        n = mom[0]
+        lv = [mom[lay.level + 4 * c:lay.level + 4 * c + 4] for c in range(lay.L)]
+        return dict(n_c=[cnt(v[0]) for v in lv], n_clipped_c=[cnt(v[1]) for v in lv],
+                    rmse_g_c=[math.sqrt(v[2] / v[0]) if v[0] > 0 and v[2] >= 0 else float("nan")
+                              for v in lv],
+                    ipw_c=[v[3] / n if n > 0 else float("nan") for v in lv])
+
+    def __getitem__(self, lev) -> AteResult:
+        return self.apo[self.levels.index(lev)]
+
+    def contrasts(self, reference=None) -> list:
+        """The L - 1 effects theta_c - theta_reference (ascending c; no GPU work), each with
+        its pointwise and its simultaneous bounds. ``reference``: one of ``levels`` (default:
+        the result's own); another reference draws its own band from the same seed."""
+        ref = self.reference if reference is None else reference
+        if ref not in self.levels:
+            raise ValueError(f"reference {ref!r} is not a treatment level: {self.levels}")
+        r = self.levels.index(ref)
+        ccov = contrast_cov(self.cov, r)
+        crit = self.crit if self.levels[r] == self.reference else \
+            band_crit(ccov, self.seed, self.level, self.n_boot)
+        out = []
+        for j, c in enumerate(c for c in range(len(self.levels)) if c != r):
+            d = self.apo[c].ate - self.apo[r].ate
+            var = ccov[j][j]
+            se = math.sqrt(max(var, 0.0)) if var == var else float("nan")
+            out.append(ApoContrast(self.levels[c], self.levels[r], d, se, d - Z * se, d + Z * se,
+                                   d - crit * se, d + crit * se))
+        return out
+
+    def wald(self) -> WaldTest:
+        """The chi-square test of "all L means are equal": delta' V^-1 delta over the L - 1
+        contrasts against the reference (the statistic does not depend on which), with L - 1
+        degrees of freedom. NaN when the contrasts' covariance is singular."""
+        r = self.levels.index(self.reference)
+        ccov = contrast_cov(self.cov, r)
+        k = len(ccov)
+        delta = [self.apo[c].ate - self.apo[r].ate for c in range(len(self.levels)) if c != r]
+        nan = float("nan")
+        if any(not (v == v) for row in ccov for v in row):
+            return WaldTest(nan, k, nan)
+        Lc = _chol_psd(ccov)
+        if any(Lc[j][j] <= 0.0 for j in range(k)):
+            return WaldTest(nan, k, nan)
+        u = []
+        for i in range(k):                              # forward solve L u = delta
+            u.append((delta[i] - sum(Lc[i][q] * u[q] for q in range(i))) / Lc[i][i])
+        stat = sum(v * v for v in u)
+        return WaldTest(stat, k, _chi2_sf(stat, k))
+
+    def rows(self):
+        d = self.diagnostics
+        get = lambda k, c: d[k][c] if k in d else None
+        return [{"level": self.levels[c], "apo": r.ate, "se": r.se, "lower_ci": r.lower_ci,
+                 "upper_ci": r.upper_ci, "n_c": get("n_c", c), "n_clipped_c": get("n_clipped_c", c),
+                 "rmse_g_c": get("rmse_g_c", c), "ipw_c": get("ipw_c", c)}
+                for c, r in enumerate(self.apo)]
+
+    def table(self) -> str:
+        d = self.diagnostics
+        w = self.wald()
+        lines = [f"{self.method}: n {d.get('n', '?')}, {len(self.levels)} levels, joint "
+                 f"{self.level:.0%} band over the contrasts, crit {self.crit:.4f} "
+                 f"({self.n_boot} draws)",
+                 f"{'level':>12s} {'n_c':>8s} {'clipped':>8s} {'E[Y(c)]':>9s} {'SE':>9s} "
+                 f"{'lower_ci':>9s} {'upper_ci':>9s} {'rmse_g':>8s} {'ipw/n':>7s}"]
+        num = lambda v, f: format(v, f) if isinstance(v, (int, float)) else "?"
+        for r in self.rows():
+            lines.append(f"{str(r['level']):>12s} {num(r['n_c'], '8d')} "
+                         f"{num(r['n_clipped_c'], '8d')} {r['apo']:9.4f} {r['se']:9.4f} "
+                         f"{r['lower_ci']:9.4f} {r['upper_ci']:9.4f} {num(r['rmse_g_c'], '8.4f')} "
+                         f"{num(r['ipw_c'], '7.3f')}")
+        lines.append(f"{'contrast':>12s} {'effect':>9s} {'SE':>9s} {'lower_ci':>9s} "
+                     f"{'upper_ci':>9s} {'lower_jt':>9s} {'upper_jt':>9s}")
+        for c in self.contrasts():
+            lines.append(f"{str(c.level) + ' - ' + str(c.reference):>12s} {c.effect:9.4f} "
+                         f"{c.se:9.4f} {c.lower_ci:9.4f} {c.upper_ci:9.4f} {c.lower_joint:9.4f} "
+                         f"{c.upper_joint:9.4f}")
+        lines.append(f"all means equal: chi2({w.df}) = {w.stat:.3f}, p = {w.p_value:.4g}")
+        return "\n".join(lines)
+
+    def json(self) -> str:
+        keep = lambda d: {k: (v if isinstance(v, (int, float, str, bool, list, type(None)))
+                              else str(v)) for k, v in d.items()}
+        return json.dumps({"method": self.method, "levels": self.levels,
+                           "reference": self.reference, "apo": self.rows(), "cov": self.cov,
+                           "contrasts": [asdict(c) for c in self.contrasts()],
+                           "crit": self.crit, "n_boot": self.n_boot, "level": self.level,
+                           "seed": self.seed, "wald": asdict(self.wald()),
+                           "moments": self.moments, "diagnostics": keep(self.diagnostics)},
+                          default=str)
+
+    to_json = json
+
+
 def results_frame(results):
     import pandas as pd
     return pd.DataFrame([r.row() for r in results])

@@ -42,7 +42,16 @@ the grouped path launch of ``cv_lognet_groups`` (K * K problems, one launch) bes
 was without it, K ``cv_lognet`` calls back to back on the K training panels (plain K-fold
 panels of the same rows without fold k), alternated; and the logistic-link score pass beside
 the identity one on the same coefficients, alternated in batches as for ``--targets``.
-Recorded in profiles/irm_logit/README.md."""
+Recorded in profiles/irm_logit/README.md.
+
+``--apos L``: the mean potential outcomes of an L-arm treatment (``estimators/apos.py``) on a
+host-built level-split panel of ``data.dgp.make_multiarm_data`` (n rows, p covariates, --dtype;
+column-major): the captured ``apos_phases`` call, its fit phase alone (the path launch or
+launches with their glue) on the call's Gram stack, and the potential-outcome pass
+(``ate_apo_moments``) in batches as for ``--targets``. At L = 2 the 8-moment pass
+(``ate_irm_score_moments``) runs on the same panel with the rows (g_0, g_1, m_1), alternated
+with it in the same process, and the JSON line says whether the shared sums have the same
+bits. Recorded in profiles/apos/README.md."""
 import argparse
 import json
 import os
@@ -74,6 +83,8 @@ def main():
                     help="time the LATE of the interactive IV model beside the ATE")
     ap.add_argument("--iivm-col", type=int, default=16,
                     help="--iivm: the exactly-binary covariate x{J} taken as the treatment D")
+    ap.add_argument("--apos", type=int, default=0, metavar="L",
+                    help="time the potential outcomes of an L-arm treatment (2..8)")
     ap.add_argument("--propensity", default="linear", choices=["linear", "logit"],
                     help="logit: time the binomial CV-LASSO propensity beside the linear one")
     a = ap.parse_args()
@@ -88,6 +99,8 @@ def main():
     n, K = int(a.n), a.folds
     blocked = bool(a.blocked) and a.dtype == "bf16"
     kw = dict(p=a.p, folds=K, seed=a.seed, dtype=a.dtype, device=dev, blocked=blocked, dgp=a.dgp)
+    if a.apos:
+        return apos(a, n, K)
     if a.repeats > 0:
         return repeated(a, n, K, kw)
     if a.targets is not None:
@@ -478,6 +491,102 @@ def iivm(a, n, K, kw):
     r = LateResult.from_moments("iivm", lat()["mom"].cpu().numpy())
     out["late"] = json.loads(r.json())
     out["irm_res"] = ate()["res"].cpu().tolist()
+    print(json.dumps(out))
+
+
+def apos(a, n, K):
+    import numpy as np
+    import torch
+    from ate_replication_causalml_amd.data.dgp import make_multiarm_data
+    from ate_replication_causalml_amd.estimators import apos as DA
+    from ate_replication_causalml_amd.estimators import irm as DI
+    from ate_replication_causalml_amd.ops.panel import build_panel
+    from ate_replication_causalml_amd.parallel import rng
+    from ate_replication_causalml_amd.result import ApoResult, apo_layout
+    from ate_replication_causalml_amd.utils.graphs import SegmentedStep
+    L = a.apos
+    dev = torch.device("cuda:0")
+    d = make_multiarm_data(n, a.seed, levels=L, p_extra=max(a.p - 21, 0))
+    level = d.D.astype(np.int64)
+    seg = L * rng.fold_ids(n, K, a.seed, 0) + level
+    # the panel of level_split_panel with the level in column W too, for the 8-moment pass
+    tg = {"D": d.D, **{f"I{c}": (level == c).astype(np.float64) for c in range(L)}}
+    pan = build_panel(d.X, d.D, d.Y, folds=seg, dtype=a.dtype, device=dev, nseg=L * K, targets=tg)
+    counts = np.asarray(pan.seg_nreal, dtype=np.float64)
+    torch.cuda.synchronize()
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = f()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    phases = DA.apos_phases(pan, K, L, "min", a.clip, seg_counts=counts)
+    call = SegmentedStep(phases, graph=True, warmup=1)
+    for _ in range(a.warmup):
+        st = call()
+    torch.cuda.synchronize()
+    coef, G = st["coef"].clone(), st["G"].clone()
+    fit_phase = DA.apos_fit_phases(pan, K, L, "min", seg_counts=counts)[0][-1]
+    c3 = coef[:, [0, 1, 3]].contiguous() if L == 2 else None
+    nb = max(a.pass_batch, 1)
+
+    def batch(f, *args):
+        def g():
+            for _ in range(nb):
+                out = f(*args)
+            return out
+        return g
+
+    p_apo = batch(DA.apo_moments, pan, coef, L, a.clip)
+    p_irm = batch(DI.irm_score_moments, pan, c3, a.clip, 2) if L == 2 else None
+    for _ in range(a.warmup):
+        fit_phase({"G": G})
+        p_apo()
+        if p_irm:
+            p_irm()
+    torch.cuda.synchronize()
+    ms = {"call": [], "fit": [], "pass_apo": []}
+    if p_irm:
+        ms["pass8"] = []
+    for _ in range(a.calls):                      # alternate: all see the same clocks
+        ms["call"].append(timed(call)[0])
+        ms["fit"].append(timed(lambda: fit_phase({"G": G}))[0])
+        t, mom = timed(p_apo)
+        ms["pass_apo"].append(t / nb)
+        if p_irm:
+            t, m8 = timed(p_irm)
+            ms["pass8"].append(t / nb)
+    esz = pan.data.element_size()
+    rows = counts.reshape(K, L)
+    ntarget = 5 if a.dtype == "bf16" else 3                      # one, Y (hi / lo), D (hi / lo)
+    union = [[int(((coef[k, :L, 1:] != 0).any(0) | (coef[k, L + c, 1:] != 0)).sum())
+              for c in range(L)] for k in range(K)]
+    out = {"mode": "apos", "levels": L, "n": n, "p": len(pan.xcols), "folds": K, "dtype": a.dtype,
+           "calls": a.calls, "pass_batch": nb, "graphed": call.graphed,
+           "path_launches": len(DA.path_launches(2 * L * K, K)), "moments": apo_layout(L).size,
+           "union": union, "nbx_apo": DA.default_nbx(pan, L),
+           "bytes_apo": int(sum(rows[k, c] * (union[k][c] + ntarget) * esz
+                                for k in range(K) for c in range(L)))}
+    for name, v in ms.items():
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "mean_ms": statistics.fmean(v), "spread_ms": max(v) - min(v)}
+    out["pass_apo"]["TB_per_s"] = out["bytes_apo"] / (out["pass_apo"]["median_ms"] * 1e-3) / 1e12
+    if p_irm:
+        lay = apo_layout(2)
+        mine = [lay.level + 2, lay.level + 6, 0, lay.level + 4]
+        # each pass is timed on its own default grid; the shared sums are compared at one nbx
+        same = DA.apo_moments(pan, coef, 2, a.clip, nbx=512 if a.dtype == "bf16" else 256)
+        out["shared_bits"] = bool(torch.equal(same[mine], m8[[5, 4, 2, 7]]))
+        out["nbx"] = [DA.default_nbx(pan, 2), 512 if a.dtype == "bf16" else 256]
+        out["ratio_pass_apo_over_pass8"] = out["pass_apo"]["median_ms"] / out["pass8"]["median_ms"]
+    r = ApoResult.from_moments("apos", call()["mom"].cpu().numpy(), list(range(L)), n=n)
+    out["apo"] = [x.ate for x in r.apo]
+    out["apo_true"] = [float(v) for v in d.apo_true]
+    out["contrasts"] = [(c.effect, c.se) for c in r.contrasts()]
+    out["crit"] = r.crit
     print(json.dumps(out))
 
 
