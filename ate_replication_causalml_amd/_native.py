@@ -99,6 +99,10 @@ _SIGS = {
     "ate_dml_resid_moments": "ipllpipipiiiiiippp",
     "ate_dml_resid_moments_final": "ipllpipipiiiiii" + "ppppp",
     "ate_dml_resid_exact": "pllpipipiiiiiiippp",
+    "ate_dml_resid_terms": "ipllpipipiiiiii" + "ppp",
+    "ate_cluster_chunk": "",
+    "ate_cluster_work": "l",
+    "ate_cluster_moments": "pplpplipppp",
     "ate_irm_score_moments": "ipllpipiipiiiiidippp",
     "ate_irm_score_moments_multi": "ipllpipiipipiiiiiidippp",
     "ate_irm_score_multi_smax": "",
@@ -164,7 +168,8 @@ _RESTYPE = {"ate_forest_scratch_bytes": ctypes.c_int64,
             "ate_scan_parts": ctypes.c_int64, "ate_group_boot_scratch": ctypes.c_int64,
             "ate_cate_moments_scratch": ctypes.c_int64,
             "ate_cate_boot_scratch": ctypes.c_int64,
-            "ate_policy_pair_hist_scratch": ctypes.c_int64}
+            "ate_policy_pair_hist_scratch": ctypes.c_int64,
+            "ate_cluster_work": ctypes.c_int64}
 _CT = {"p": c_void_p, "i": c_int, "l": c_int64, "u": c_uint64, "d": c_double}
 
 

@@ -221,13 +221,29 @@ def ate_double_ml(Y, W, X, num_trees=100, method="Double Machine Learning", run=
 
 
 def ate_dml(Y, W, X, folds=5, lambda_rule="min", method="DML cross-fit (LASSO)",
-            run=None, repeats=1, aggregate="median") -> AteResult:
+            run=None, repeats=1, aggregate="median", clusters=None) -> AteResult:
     """K-fold cross-fit partially linear DML with CV-LASSO nuisances (north-star).
     ``repeats`` > 1: repeated cross-fitting over that many distinct K-fold partitions
     (Chernozhukov et al. 2018 §3.4), ``aggregate`` "median" (default) or "mean"; the
-    partitions share one Gram pass (estimators/lasso.dml_repeated_phases)."""
+    partitions share one Gram pass (estimators/lasso.dml_repeated_phases).
+    ``clusters``: an (n,) vector of labels (integers or strings) of dependent rows -- whole
+    clusters are cross-fitted and the SE is cluster-robust (estimators/cluster.py; grf
+    ``clusters=``, DoubleML ``DoubleMLClusterData``); diagnostics gain n_clusters,
+    max_cluster, design_effect and se_unclustered. One-way clustering, ``repeats`` = 1."""
     run = _run(run)
     with trace("ate_dml", folds=folds, repeats=repeats):
+        if clusters is not None:
+            from .estimators import cluster as DC
+            if _ref(run):
+                from .reference import estimators as R
+                lay = DC.cluster_layout(clusters, len(_np(Y)), folds, run.seed, repeats=repeats)
+                return R.dml_plr_lasso(Y, W, X, folds=folds, seed=run.seed,
+                                       lambda_rule=lambda_rule, method=method,
+                                       clusters=lay.codes)
+            return DC.dml_plr_lasso_cluster(Y, W, X, clusters, folds=folds, seed=run.seed,
+                                            lambda_rule=lambda_rule, method=method,
+                                            device=run.device(), dtype=run.dtype,
+                                            repeats=repeats)
         if repeats > 1:
             if _ref(run):
                 from .reference import estimators as R
@@ -255,7 +271,7 @@ def _linear_only(propensity, what):
 
 def ate_dml_irm(Y, W, X, folds=5, lambda_rule="min", clip=0.01,
                 method="DML-IRM cross-fit (LASSO)", run=None, repeats=1,
-                aggregate="median", propensity="linear") -> AteResult:
+                aggregate="median", propensity="linear", clusters=None) -> AteResult:
     """K-fold cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1)
     with CV-LASSO nuisances: per-arm outcome regressions and the linear-probability
     propensity (clipped to [clip, 1 - clip]) on the fold Gram stack; the ATE under
@@ -267,11 +283,26 @@ def ate_dml_irm(Y, W, X, folds=5, lambda_rule="min", clip=0.01,
     (cv.glmnet(family="binomial"), all K * K fits in one launch, the score through the
     logistic link) -- as do ate_dml_irm_gate / _cate / _policy / _targets. Limits of "logit"
     (ValueError): ``repeats`` = 1, no row shards, an fp32 / fp64 panel, p <= 96, K <= 16; not
-    available for ate_dml_irm_sensitivity and ate_dml_iivm."""
+    available for ate_dml_irm_sensitivity and ate_dml_iivm.
+    ``clusters``: an (n,) vector of labels of dependent rows -- whole clusters are
+    cross-fitted and the SE is cluster-robust, as ate_dml(clusters=); either propensity,
+    ``repeats`` = 1."""
     run = _run(run)
     with trace("ate_dml_irm", folds=folds, repeats=repeats):
         from .estimators.irm import check_logit_scope
         check_logit_scope(propensity, X, folds, repeats=repeats)
+        if clusters is not None:
+            from .estimators import cluster as DC
+            if _ref(run):
+                from .reference import estimators as R
+                lay = DC.cluster_layout(clusters, len(_np(Y)), folds, run.seed, repeats=repeats)
+                return R.dml_irm_lasso(Y, W, X, folds=folds, seed=run.seed,
+                                       lambda_rule=lambda_rule, clip=clip, method=method,
+                                       propensity=propensity, clusters=lay.codes)
+            return DC.dml_irm_lasso_cluster(Y, W, X, clusters, folds=folds, seed=run.seed,
+                                            lambda_rule=lambda_rule, clip=clip, method=method,
+                                            device=run.device(), dtype=run.dtype,
+                                            propensity=propensity, repeats=repeats)
         if repeats != 1:
             if _ref(run):
                 from .reference import estimators as R

@@ -4,6 +4,7 @@
   dml        K-fold DML cross-fit on a synthetic N x p panel (the north-star job)
   late       the LATE of the interactive IV model (DML-IIVM) on a synthetic encouragement design
   apos       the mean potential outcomes of a multi-arm treatment (DML-APOS) on a synthetic mailing design
+  cluster    cluster-robust DML (PLR or IRM) on synthetic data with a cluster random effect
   build      compile the gfx950 HIP library and the host C++ library
 """
 from __future__ import annotations
@@ -264,6 +265,29 @@ def _apos(a):
     return 0
 
 
+def _cluster(a):
+    # cluster-level cross-fitting and the cluster-robust SE on the clustered design of data.dgp
+    from .api import ate_dml, ate_dml_irm
+    from .config import RunConfig
+    from .data.dgp import make_clustered_data
+    run = RunConfig(backend=a.backend, dtype=a.dtype, seed=a.seed)
+    try:
+        d = make_clustered_data(a.n, a.cluster_size, a.icc, a.seed, assign=a.assign)
+        if a.model == "irm":
+            r = ate_dml_irm(d.Y, d.W, d.X, folds=a.folds, lambda_rule=a.lambda_rule, clip=a.clip,
+                            run=run, clusters=d.clusters)
+        else:
+            r = ate_dml(d.Y, d.W, d.X, folds=a.folds, lambda_rule=a.lambda_rule, run=run,
+                        clusters=d.clusters)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    out = json.loads(r.to_json())
+    out["se_unclustered"] = r.diagnostics["se_unclustered"]
+    out["tau_true"] = d.tau_true
+    print(json.dumps(out))
+    return 0
+
+
 def _build(a):
     from . import _build as b
     b.build_all()
@@ -369,6 +393,22 @@ def main(argv=None):
     m.add_argument("--backend", default="auto", choices=["auto", "gpu", "cpu", "reference"])
     m.add_argument("--dtype", default="f64", choices=["f64", "f32", "bf16"])
     m.set_defaults(fn=_apos)
+    c = sub.add_parser("cluster")
+    c.add_argument("--n", type=int, default=50_000)
+    c.add_argument("--cluster-size", type=int, default=5, help="rows per cluster")
+    c.add_argument("--icc", type=float, default=0.3,
+                   help="intra-cluster correlation of the outcome noise, in [0, 1]")
+    c.add_argument("--assign", default="cluster", choices=["cluster", "row"],
+                   help="the treatment is drawn once per cluster, or once per row")
+    c.add_argument("--model", default="irm", choices=["irm", "plr"])
+    c.add_argument("--seed", type=int, default=1991)
+    c.add_argument("--folds", type=int, default=5)
+    c.add_argument("--clip", type=float, default=0.01,
+                   help="irm: the propensity is clipped to [clip, 1 - clip]")
+    c.add_argument("--lambda-rule", default="min", choices=["min", "1se"])
+    c.add_argument("--backend", default="auto", choices=["auto", "gpu", "cpu", "reference"])
+    c.add_argument("--dtype", default="f64", choices=["f64", "f32", "bf16"])
+    c.set_defaults(fn=_cluster)
     b = sub.add_parser("build")
     b.set_defaults(fn=_build)
     a = ap.parse_args(argv)

@@ -320,3 +320,57 @@ def make_multiarm_data(n: int = 50_000, seed: int = 1991, levels: int = 5, p_ext
     arms = [ARM_NAMES[c] if c < len(ARM_NAMES) else f"arm{c}" for c in range(levels)]
     return MultiArmData(X=X, Y=Y, D=D, names=list(d.names), arms=arms,
                         apo_true=p_all.mean(axis=0), propensity=prob)
+
+
+S_CL_U = 75         # clustered data: the cluster random effect
+S_CL_E = 76         # clustered data: the row noise
+S_CL_W = 77         # clustered data: the treatment (drawn per cluster or per row)
+
+CLUSTER_TAU = 0.2   # the constant effect of make_clustered_data: PLR and IRM estimate the same
+
+
+@dataclass
+class ClusteredData:
+    X: np.ndarray          # (n, p) float64, the tutorial's covariates
+    Y: np.ndarray          # (n,) float64, continuous
+    W: np.ndarray          # (n,) float64 in {0,1}
+    clusters: np.ndarray   # (n,) int64 cluster label of every row
+    names: list
+    tau_true: float
+
+    @property
+    def n(self):
+        return self.X.shape[0]
+
+
+def make_clustered_data(n: int = 50_000, cluster_size: int = 5, icc: float = 0.3,
+                        seed: int = 1991, assign: str = "cluster", p_extra: int = 0,
+                        params: DgpParams = TUTORIAL) -> ClusteredData:
+    """Rows that are dependent within clusters, on the tutorial's covariates
+    (``make_tutorial_data``): row i belongs to cluster i // cluster_size, and with s = sigmoid
+
+        Y = 0.5 yob + 0.3 g2000 + CLUSTER_TAU W + sqrt(icc) u_c + sqrt(1 - icc) e_i,
+        u_c, e_i ~ N(0, 1): ``icc`` is the intra-cluster correlation of the noise
+        assign="cluster": W_c ~ Bern(0.5), one draw per cluster (a cluster-randomised trial:
+                          the i.i.d. SE is too small by about sqrt(1 + (m - 1) icc))
+        assign="row":     W_i ~ Bern(s(0.5 yob)), one draw per row (the score's cluster sums
+                          largely cancel: the two SEs are close)
+
+    Every draw is a Philox function of (seed, stream, row or cluster)."""
+    if assign not in ("cluster", "row"):
+        raise ValueError(f'assign must be "cluster" or "row", got {assign!r}')
+    if cluster_size < 1 or not 0.0 <= icc <= 1.0:
+        raise ValueError("cluster_size must be >= 1 and icc in [0, 1]")
+    d = make_tutorial_data(n, seed, p_extra, params)
+    col = {k: d.X[:, j] for j, k in enumerate(d.names)}
+    idx = np.arange(n, dtype=np.uint64)
+    cl = (idx // np.uint64(cluster_size)).astype(np.int64)
+    cid = cl.astype(np.uint64)
+    if assign == "cluster":
+        W = (_uniform(seed, S_CL_W, cid) < 0.5).astype(np.float64)
+    else:
+        W = (_uniform(seed, S_CL_W, idx) < 1.0 / (1.0 + np.exp(-0.5 * col["yob"]))).astype(
+            np.float64)
+    Y = 0.5 * col["yob"] + 0.3 * col["g2000"] + CLUSTER_TAU * W + \
+        np.sqrt(icc) * _normal(seed, S_CL_U, cid) + np.sqrt(1.0 - icc) * _normal(seed, S_CL_E, idx)
+    return ClusteredData(X=d.X, Y=Y, W=W, clusters=cl, names=list(d.names), tau_true=CLUSTER_TAU)

@@ -715,7 +715,7 @@ def irm_repeated_panel(pan, folds: int, repeats: int, lambda_rule="min", clip=0.
 
 # ---------------------------------------------------------------- the shared front end
 def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts=None,
-                    check_extra=None, cells=check_cells, targets=None):
+                    check_extra=None, cells=check_cells, targets=None, fold_ids=None):
     """The prologue of every ``dml_irm_*`` estimator: the binary-W check, the fold ids, the
     (global) rows per (fold, arm) cell and the arm-split panel (segment 2k + a = fold k,
     W = a) on ``device``. Returns (pan, counts [2K], extra, n_total, rid).
@@ -727,12 +727,13 @@ def arm_split_panel(Y, W, X, folds, seed, dtype, device, dist=None, extra_counts
     cells: the check of the cell counts, ``cells(counts, folds)`` (repeated cross-fitting
     passes its own: its K*K micro-groups may have an empty arm). targets: further named
     target columns of the panel (``build_panel(targets=)``; estimators/late.py: the treatment
-    taken D beside the instrument in column W)."""
+    taken D beside the instrument in column W). fold_ids: an explicit fold of every row
+    (estimators/cluster.py: whole clusters per fold) instead of the Philox assignment."""
     dev = resolve_device(device)
     Yn, Wn, Xn = as_np(Y), as_np(W), as_np(X)
     if not np.isin(Wn, (0.0, 1.0)).all():
         raise ValueError("DML-IRM needs a binary treatment: W must be exactly 0 or 1")
-    fid = _fold_ids(len(Yn), folds, seed, 0, dist)
+    fid = _fold_ids(len(Yn), folds, seed, 0, dist) if fold_ids is None else fold_ids
     seg = 2 * np.asarray(fid, dtype=np.int64) + Wn.astype(np.int64)
     counts = np.bincount(seg, minlength=2 * folds).astype(np.float64)
     extra = None if extra_counts is None else np.asarray(extra_counts, dtype=np.float64)

@@ -321,16 +321,60 @@ def causal_forest_ate(Y, W, X, num_trees=2000, seed=12345, method="Causal Forest
                           se_bad=float(np.sqrt(np.nanmean(cf.var_oob))))
 
 
+# ---------------------------------------------------------------- cluster-robust inference
+def cluster_codes(clusters):
+    """(codes, J): the labels of ``clusters`` as integers 0..J-1 in sorted label order."""
+    labels, codes = np.unique(np.asarray(clusters), return_inverse=True)
+    return codes.reshape(-1).astype(np.int64), len(labels)
+
+
+def cluster_fold_ids(clusters, folds, seed):
+    """The fold of every row when whole clusters are cross-fitted: cluster j (sorted label
+    order) goes to fold ``rng.fold_ids(J, folds, seed, 0)[j]`` and each of its rows with it
+    (balanced over clusters, not rows; singleton clusters give the row-level folds)."""
+    codes, J = cluster_codes(clusters)
+    return rng.fold_ids(J, folds, seed, stream=0)[codes]
+
+
+def cluster_se(a, b, theta, codes, correction):
+    """The cluster-robust SE of the solution theta of sum_i (a_i - theta b_i) = 0 (b None:
+    b == 1): with t_j = sum_{i in j} (a_i - theta b_i), Var = sum_j t_j^2 / (sum_i b_i)^2,
+    times J / (J - 1) when ``correction`` is set (the n - 1 rule of the mean)."""
+    a = _arr(a)
+    b = np.ones_like(a) if b is None else _arr(b)
+    codes = np.asarray(codes, dtype=np.int64)
+    J = int(codes.max()) + 1
+    A, B = np.zeros(J), np.zeros(J)
+    np.add.at(A, codes, a)
+    np.add.at(B, codes, b)
+    t = A - theta * B
+    var = (t * t).sum() / B.sum() ** 2
+    if correction:
+        var *= J / (J - 1)
+    return float(np.sqrt(var))
+
+
+def _cluster_diag(codes, J, se_unclustered):
+    nj = np.bincount(codes, minlength=J).astype(np.float64)
+    return dict(n_clusters=J, max_cluster=int(nj.max()),
+                design_effect=float((nj * nj).sum() / len(codes)),
+                se_unclustered=float(se_unclustered))
+
+
 # ---------------------------------------------------------------- K-fold DML (north star)
 def dml_plr_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min",
-                  method="DML cross-fit (LASSO)", fold_ids=None):
+                  method="DML cross-fit (LASSO)", fold_ids=None, clusters=None):
     """Partially-linear DML with K-fold cross-fitting and CV-LASSO nuisances.
 
     For held-out fold k the nuisances E[Y|X], E[W|X] are gaussian LASSO fits on
     the other K-1 folds, with lambda chosen by (K-1)-fold CV over those same
     folds (so every Gram the GPU needs is a sum of per-fold Grams). ``fold_ids``:
-    an explicit fold of every row (default: the Philox assignment)."""
+    an explicit fold of every row (default: the Philox assignment). ``clusters``: (n,)
+    labels -- whole clusters are cross-fitted (:func:`cluster_fold_ids`) and the SE is the
+    cluster-robust one (:func:`cluster_se`, no correction)."""
     Y, W, X = _arr(Y), _arr(W), _arr(X)
+    if clusters is not None:
+        fold_ids = cluster_fold_ids(clusters, folds, seed)
     fid = rng.fold_ids(len(Y), folds, seed, stream=0) if fold_ids is None else \
         np.asarray(fold_ids, dtype=np.int64)
     yr = np.empty_like(Y)
@@ -344,7 +388,12 @@ def dml_plr_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min",
             cv = gn.cv_glmnet(X[tr], target[tr], foldid=inner)
             s = "lambda.min" if lambda_rule == "min" else "lambda.1se"
             out[te] = target[te] - cv.predict(X[te], s=s)
-    return dml_from_residuals(yr, wr, method)
+    r = dml_from_residuals(yr, wr, method)
+    if clusters is None:
+        return r
+    codes, J = cluster_codes(clusters)
+    se = cluster_se(wr * yr, wr * wr, r.ate, codes, correction=False)
+    return AteResult.make(method, r.ate, se, n=len(Y), **_cluster_diag(codes, J, r.se))
 
 
 PROPENSITIES = ("linear", "logit")
@@ -390,20 +439,30 @@ def _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids=None, propensi
 
 
 def dml_irm_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min", clip=0.01,
-                  method="DML-IRM cross-fit (LASSO)", fold_ids=None, propensity="linear"):
+                  method="DML-IRM cross-fit (LASSO)", fold_ids=None, propensity="linear",
+                  clusters=None):
     """Cross-fitted AIPW for the interactive model (Chernozhukov et al. 2018 §5.1) with
     CV-LASSO nuisances, row by row in float64: for held-out fold k, g0 and g1 are gaussian
     LASSO fits of Y on the training rows of each arm and m is the linear-probability LASSO of
     W on all training rows, each with lambda chosen by (K-1)-fold CV over the training folds
     (as dml_plr_lasso). Score (textbook signs): psi = g1 - g0 + W (Y - g1) / m
     - (1 - W)(Y - g0) / (1 - m) with m clipped to [clip, 1 - clip]; theta = mean(psi),
-    SE = sd(psi) / sqrt(n)."""
+    SE = sd(psi) / sqrt(n). ``clusters``: (n,) labels -- whole clusters are cross-fitted
+    (:func:`cluster_fold_ids`) and the SE is the cluster-robust one (:func:`cluster_se` with
+    the J / (J - 1) correction)."""
     Y, W, X = _arr(Y), _arr(W), _arr(X)
+    if clusters is not None:
+        fold_ids = cluster_fold_ids(clusters, folds, seed)
     psi, g0, g1, m = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids, propensity)
     n = len(Y)
     nt = W.sum()
     extra = {} if propensity == "linear" else {"propensity": propensity}
-    return AteResult.make(method, psi.mean(), psi.std(ddof=1) / np.sqrt(n), n=n, **extra,
+    se = psi.std(ddof=1) / np.sqrt(n)
+    if clusters is not None:
+        codes, J = cluster_codes(clusters)
+        extra.update(_cluster_diag(codes, J, se))
+        se = cluster_se(psi, None, psi.mean(), codes, correction=True)
+    return AteResult.make(method, psi.mean(), se, n=n, **extra,
                           n_clipped=int(((m < clip) | (m > 1 - clip)).sum()),
                           n_treated=int(nt),
                           rmse_g0=float(np.sqrt(((1 - W) * (Y - g0) ** 2).sum() / (n - nt))),

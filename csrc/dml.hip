@@ -54,11 +54,15 @@ __device__ int compact_support(C* cy, C* cw, int* xc, int p, int* wcnt /* [>= 4]
   return base;
 }
 
-template <typename T, int RPT, bool AGENT = false>
+// TERMS: instead of summing moments, write every row's a = wr yr and b = wr^2 (ta, tb: [ld]
+// fp64 in panel row order, 0 on padding rows) -- the per-row terms of the cluster-robust
+// variance (csrc/cluster.hip); `partial` is not touched then.
+template <typename T, int RPT, bool AGENT = false, bool TERMS = false>
 __device__ __forceinline__ void dml_resid_body(
     const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p,
     const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef /*[nseg][2][p+1]*/,
-    int y0, int y1, int w0, int w1, int vcol, double* __restrict__ partial) {
+    int y0, int y1, int w0, int w1, int vcol, double* __restrict__ partial,
+    double* __restrict__ ta = nullptr, double* __restrict__ tb = nullptr) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
   double* cy = sh;                    // [p+1]
   double* cw = sh + (p + 1);          // [p+1]
@@ -101,14 +105,19 @@ __device__ __forceinline__ void dml_resid_body(
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
       if (ii[r] >= sg.r1) continue;
-      if (ld_col(X, ld, vcol, ii[r]) == 0.0) continue;
+      if (ld_col(X, ld, vcol, ii[r]) == 0.0) {
+        if constexpr (TERMS) { ta[ii[r]] = 0.0; tb[ii[r]] = 0.0; }
+        continue;
+      }
       double y = ld_col(X, ld, y0, ii[r]) + (y1 >= 0 ? ld_col(X, ld, y1, ii[r]) : 0.0);
       double w = ld_col(X, ld, w0, ii[r]) + (w1 >= 0 ? ld_col(X, ld, w1, ii[r]) : 0.0);
       double yr = y - py[r], wr = w - pw[r], w2 = wr * wr;
+      if constexpr (TERMS) { ta[ii[r]] = wr * yr; tb[ii[r]] = w2; continue; }
       v[0] += wr * yr; v[1] += w2; v[2] += yr * yr * w2; v[3] += yr * w2 * wr; v[4] += w2 * w2;
       v[5] += 1.0; v[6] += yr * yr;
     }
   }
+  if constexpr (TERMS) return;
   block_sum<7>(v, red);
   if (threadIdx.x == 0) {
     double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 7;
@@ -162,12 +171,15 @@ static int dml_resid_t(const void* X, int64_t ld, const void* xcols, int p, cons
 // 2 = per-term int64 limb sums at the shifts sh[7] derived from the global max
 // (partial [blocks][14] int64: hi limbs, then lo limbs) -- integer sums, so the block and
 // the rank that own a row cannot change the result.
-template <bool AGENT = false>
+// TERMS (mode 0): the per-row terms a = wr yr, b = wr^2 instead of the moments, as
+// dml_resid_body.
+template <bool AGENT = false, bool TERMS = false>
 __device__ __forceinline__ void dml_resid_bf16_body(
     const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
     const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef,
     int y0, int y1, int w0, int w1, int vcol, double* __restrict__ partial, int mode,
-    const int64_t* __restrict__ sh) {
+    const int64_t* __restrict__ sh, double* __restrict__ ta = nullptr,
+    double* __restrict__ tb = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float shf[];
   float* cy = shf;                 // [p+1]
   float* cw = shf + (p + 1);       // [p+1]
@@ -223,10 +235,14 @@ __device__ __forceinline__ void dml_resid_bf16_body(
     if (w1 >= 0) ld8(w1, i, wb); else { for (int r = 0; r < 8; ++r) wb[r] = 0.f; }
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-      if (vv[r] == 0.f) continue;
+      if (vv[r] == 0.f) {
+        if constexpr (TERMS) { ta[i + r] = 0.0; tb[i + r] = 0.0; }
+        continue;
+      }
       const double yr = ((double)ya[r] + (double)yb[r]) - (double)py[r];
       const double wr = ((double)wa[r] + (double)wb[r]) - (double)pw[r];
       const double w2 = wr * wr;
+      if constexpr (TERMS) { ta[i + r] = wr * yr; tb[i + r] = w2; continue; }
       if (mode == 0) {
         v[0] += wr * yr; v[1] += w2; v[2] += yr * yr * w2; v[3] += yr * w2 * wr; v[4] += w2 * w2;
         v[5] += 1.0; v[6] += yr * yr;
@@ -246,6 +262,7 @@ __device__ __forceinline__ void dml_resid_bf16_body(
       }
     }
   }
+  if constexpr (TERMS) return;
   const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
   if (mode == 0) {
     block_sum<7>(v, red);
@@ -417,6 +434,57 @@ ATE_API int ate_dml_resid_moments(int dtype, const void* X, int64_t cs, int64_t 
     return 0;
   }
   return -1;
+}
+
+// ------------------------------------------------------------------ per-row score terms
+template <typename T, int RPT>
+__global__ __launch_bounds__(256) void dml_resid_terms_kernel(
+    const T* __restrict__ X, int64_t ld, const int* __restrict__ xcols, int p,
+    const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef, int y0, int y1,
+    int w0, int w1, int vcol, double* __restrict__ ta, double* __restrict__ tb) {
+  dml_resid_body<T, RPT, false, true>(X, ld, xcols, p, segs, nseg, coef, y0, y1, w0, w1, vcol,
+                                      nullptr, ta, tb);
+}
+
+__global__ __launch_bounds__(256) void dml_resid_terms_bf16_kernel(
+    const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int* __restrict__ xcols, int p,
+    const Seg* __restrict__ segs, int nseg, const double* __restrict__ coef, int y0, int y1,
+    int w0, int w1, int vcol, double* __restrict__ ta, double* __restrict__ tb) {
+  dml_resid_bf16_body<false, true>(X, cs, bs, xcols, p, segs, nseg, coef, y0, y1, w0, w1, vcol,
+                                   nullptr, 0, nullptr, ta, tb);
+}
+
+// The held-out residual pass of ate_dml_resid_moments -- same arguments, same dot products,
+// same residuals -- writing every row's a = wr yr and b = wr^2 (ta, tb: [ld] fp64, panel row
+// order, 0 on padding rows) instead of summing moments. The segments must tile [0, ld):
+// every row is written. bf16: every segment starts and ends on a multiple of 8 rows.
+ATE_API int ate_dml_resid_terms(int dtype, const void* X, int64_t cs, int64_t bs,
+                                const void* xcols, int p, const void* segs, int nseg,
+                                const void* coef, int y0, int y1, int w0, int w1, int vcol,
+                                int nbx, void* ta, void* tb, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype != 3 && bs != 64) return -1;
+  if (nbx < 1 || nseg < 1 || !ta || !tb) return -1;
+  dim3 grid(nbx, nseg);
+  const size_t shd = (size_t)2 * (p + 1) * sizeof(double) + (size_t)p * sizeof(int);
+  if (dtype == 1) {
+    ATE_LAUNCH((dml_resid_terms_kernel<float, 4>), grid, dim3(256), shd, s, (const float*)X, cs,
+               (const int*)xcols, p, (const Seg*)segs, nseg, (const double*)coef, y0, y1, w0, w1,
+               vcol, (double*)ta, (double*)tb);
+  } else if (dtype == 2) {
+    ATE_LAUNCH((dml_resid_terms_kernel<double, 4>), grid, dim3(256), shd, s, (const double*)X,
+               cs, (const int*)xcols, p, (const Seg*)segs, nseg, (const double*)coef, y0, y1, w0,
+               w1, vcol, (double*)ta, (double*)tb);
+  } else if (dtype == 3) {
+    const size_t sh = (size_t)2 * (p + 1) * sizeof(float) + (size_t)p * sizeof(int);
+    ATE_LAUNCH(dml_resid_terms_bf16_kernel, grid, dim3(256), sh, s, (const bf16_t*)X, cs, bs,
+               (const int*)xcols, p, (const Seg*)segs, nseg, (const double*)coef, y0, y1, w0, w1,
+               vcol, (double*)ta, (double*)tb);
+  } else {
+    return -1;
+  }
+  ATE_CHECK_LAUNCH();
+  return 0;
 }
 
 // exact-mode passes of the bf16 residual kernel (mode 1: per-block max |term| into

@@ -51,7 +51,19 @@ launches with their glue) on the call's Gram stack, and the potential-outcome pa
 (``ate_apo_moments``) in batches as for ``--targets``. At L = 2 the 8-moment pass
 (``ate_irm_score_moments``) runs on the same panel with the rows (g_0, g_1, m_1), alternated
 with it in the same process, and the JSON line says whether the shared sums have the same
-bits. Recorded in profiles/apos/README.md."""
+bits. Recorded in profiles/apos/README.md.
+
+``--clusters``: the cluster-robust call (``estimators/cluster.py``) beside the plain ATE on the
+same arm-split panel, for four cluster-size profiles over the panel's real rows (singletons,
+households of 1-6, 50 equal clusters, one cluster of half the rows plus singletons; clusters
+are consecutive runs of panel rows, the shape the front end produces): per profile the two
+launches of the cluster pass (``ate_cluster_moments``) and, once, the per-row score pass
+(``ate_irm_scores``) and the 8-moment pass, in batches as for ``--targets``; then one captured
+clustered call per profile and one captured ``irm_phases`` call, alternated. The JSON line
+carries the pass's byte model (12 n + 8 J) and its rate. With ``--score-only``: after one fit, 5
+launches of the cluster pass per profile and of the score pass, for a separate ``rocprofv3
+--kernel-trace --stats`` run (the two cluster kernels are told apart by name). Recorded in
+profiles/cluster/README.md."""
 import argparse
 import json
 import os
@@ -87,6 +99,8 @@ def main():
                     help="time the potential outcomes of an L-arm treatment (2..8)")
     ap.add_argument("--propensity", default="linear", choices=["linear", "logit"],
                     help="logit: time the binomial CV-LASSO propensity beside the linear one")
+    ap.add_argument("--clusters", action="store_true",
+                    help="time the cluster-robust call for four cluster-size profiles")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -101,6 +115,8 @@ def main():
     kw = dict(p=a.p, folds=K, seed=a.seed, dtype=a.dtype, device=dev, blocked=blocked, dgp=a.dgp)
     if a.apos:
         return apos(a, n, K)
+    if a.clusters:
+        return clusters(a, n, K, kw)
     if a.repeats > 0:
         return repeated(a, n, K, kw)
     if a.targets is not None:
@@ -491,6 +507,127 @@ def iivm(a, n, K, kw):
     r = LateResult.from_moments("iivm", lat()["mom"].cpu().numpy())
     out["late"] = json.loads(r.json())
     out["irm_res"] = ate()["res"].cpu().tolist()
+    print(json.dumps(out))
+
+
+def cluster_profiles(nv, seed):
+    """name -> cluster sizes summing to nv, the four profiles of ``--clusters``."""
+    import numpy as np
+    rs = np.random.default_rng(seed)
+    hh = rs.integers(1, 7, size=nv // 3 + 8)
+    hh = hh[:int(np.searchsorted(np.cumsum(hh), nv)) + 1]
+    hh[-1] -= hh.sum() - nv
+    eq = np.full(50, nv // 50)
+    eq[:nv % 50] += 1
+    return {"singletons": np.ones(nv, dtype=np.int64), "households_1_6": hh[hh > 0],
+            "equal_50": eq, "half_plus_singletons": np.r_[nv // 2, np.ones(nv - nv // 2,
+                                                                           dtype=np.int64)]}
+
+
+def clusters(a, n, K, kw):
+    import numpy as np
+    import torch
+    from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
+    from ate_replication_causalml_amd.estimators import cluster as DC
+    from ate_replication_causalml_amd.estimators import irm as DI
+    from ate_replication_causalml_amd.ops.gram import plan_slot
+    from ate_replication_causalml_amd.utils.graphs import GraphedStep, SegmentedStep
+    split = synthetic_panel(n, arm_split=True, **kw)
+    torch.cuda.synchronize()
+    dev = split.device
+    order = torch.nonzero(split.row_index >= 0).flatten().to(torch.int32)   # panel rows, ascending
+    nv = order.numel()
+    prof = {}
+    for name, sizes in cluster_profiles(nv, a.seed).items():
+        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        assert starts[-1] == nv
+        prof[name] = (torch.from_numpy(starts).to(dev), len(sizes), int(sizes.max()))
+    counts = tuple(float(c) for c in split.seg_nreal)
+    st = DI.run_phases(DI.irm_phases(split, K, "min", a.clip))
+    coef, theta = st["coef"].clone(), st["res"][:1].clone()
+    psi = DI.irm_scores(split, coef, a.clip, 2)
+    torch.cuda.synchronize()
+    out = {"mode": "clusters", "n": nv, "p": a.p, "folds": K, "dtype": a.dtype,
+           "blocked": kw["blocked"], "dgp": a.dgp, "chunk": DC.cluster_chunk(),
+           "irm_res": st["res"].cpu().tolist(), "profiles": {}}
+    if a.score_only:
+        for name, (starts, J, _) in prof.items():
+            for _ in range(5):
+                mom = DC.cluster_moments(psi, None, starts, order, J, theta)
+            out["profiles"][name] = {"J": J, "moments": mom.cpu().tolist()}
+        for _ in range(5):
+            DI.irm_scores(split, coef, a.clip, 2)
+        torch.cuda.synchronize()
+        out["launches_each"] = 5
+        print(json.dumps(out))
+        return
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = f()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), r
+
+    nb = max(a.pass_batch, 1)
+
+    def batch(f):
+        def g():
+            for _ in range(nb):
+                r = f()
+            return r
+        return g
+
+    def stats(v):
+        return {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                "mean_ms": statistics.fmean(v)}
+
+    passes = {name: batch(lambda s=starts, J=J: DC.cluster_moments(psi, None, s, order, J, theta))
+              for name, (starts, J, _) in prof.items()}
+    passes["scores"] = batch(lambda: DI.irm_scores(split, coef, a.clip, 2))
+    passes["moments8"] = batch(lambda: DI.irm_score_moments(split, coef, a.clip, 2))
+    for _ in range(a.warmup):
+        for f in passes.values():
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in passes}
+    for _ in range(a.calls):                      # alternate: all see the same clocks
+        for k, f in passes.items():
+            ms[k].append(timed(f)[0] / nb)
+    out["pass_batch"], out["calls"] = nb, a.calls
+    out["scores_pass"], out["moments8_pass"] = stats(ms["scores"]), stats(ms["moments8"])
+    with plan_slot(0):
+        plain = SegmentedStep(DI.irm_phases(split, K, "min", a.clip), graph=True, warmup=1)
+    calls = {}
+    with plan_slot(1):
+        for name, (starts, J, _) in prof.items():
+            calls[name] = GraphedStep(lambda s=starts, J=J: DC._irm_cluster_body(
+                split, s, order, K, "min", a.clip, J, counts), warmup=1)
+    for _ in range(a.warmup):
+        plain()
+        for c in calls.values():
+            c()
+    torch.cuda.synchronize()
+    cms = {k: [] for k in ("plain", *calls)}
+    for _ in range(a.calls):
+        cms["plain"].append(timed(plain)[0])
+        for k, c in calls.items():
+            cms[k].append(timed(c)[0])
+    out["plain_call"] = stats(cms["plain"])
+    out["graphed"] = plain.graphed
+    for name, (starts, J, nmax) in prof.items():
+        r = calls[name]().cpu().tolist()
+        p_ms = statistics.median(ms[name])
+        model = 12 * nv + 8 * J
+        out["profiles"][name] = {
+            "J": J, "max_cluster": nmax, "cluster_pass": stats(ms[name]), "call": stats(cms[name]),
+            "added_ms_over_plain_call": statistics.median(cms[name]) - out["plain_call"]["median_ms"],
+            "model_bytes": model, "TB_per_s": model / (p_ms * 1e-3) / 1e12,
+            "theta_se_se0": r[:3], "cluster_moments": r[3:7]}
+    base = out["profiles"]["singletons"]["cluster_pass"]["median_ms"]
+    for v in out["profiles"].values():
+        v["pass_over_singletons"] = v["cluster_pass"]["median_ms"] / base
     print(json.dumps(out))
 
 
