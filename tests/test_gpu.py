@@ -34,7 +34,8 @@ def test_native_library_loaded(gpu):
                                      ("f64", 150)])
 def test_gram_kernel_vs_fp64(gpu, dtype, p):
     # bf16: p=100 -> P=128 (128-tile kernel), 150 -> P=256 (one 256 tile),
-    # 300 -> P=512 (256-tile kernel incl. an off-diagonal tile)
+    # 300 -> P=512 (the paired-tile kernel, the default at P % 512 == 0; the 256-tile kernel's
+    # off-diagonal tiles run in test_gpu_gram_shapes at P = 768 and under tile256 at P = 512)
     rs = np.random.RandomState(0)
     n = 3001
     X = rs.randn(n, p) * np.linspace(0.5, 2, p) + np.linspace(-1, 1, p)
