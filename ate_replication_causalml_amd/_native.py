@@ -112,6 +112,9 @@ _SIGS = {
     "ate_irm_score_link": "ii" + "ipllpipiipiiiiidippp",
     "ate_iivm_moments": "ipllpipiipiiiiiiidippp",
     "ate_apo_moments": "ipllpipiipiiiiidippp",
+    "ate_pliv_lds_max": "",
+    "ate_pliv_moments": "ipllpipiippii" + "pppp",
+    "ate_pliv_terms": "ipllpipiippii" + "pppp",
     "ate_group_boot": "pppliiuippp",
     "ate_group_boot_scratch": "iii",
     "ate_cate_moments": "ppplpiiippp",

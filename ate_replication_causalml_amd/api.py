@@ -30,7 +30,9 @@ IRM(score="ATTE"), grf average_treatment_effect(target.sample=)) -> ate_dml_irm_
 the LATE with a binary instrument under noncompliance (DoubleML DoubleMLIIVM) -> ate_dml_iivm;
 the mean potential outcomes of a multi-valued treatment, their contrasts against a reference
 level and a simultaneous band (DoubleML DoubleMLAPOS / causal_contrast, grf
-multi_arm_causal_forest) -> ate_dml_apos.
+multi_arm_causal_forest) -> ate_dml_apos;
+the effect of a real treatment instrumented by 1 to 4 instruments in the partially linear IV
+model (DoubleML DoubleMLPLIV) -> ate_dml_pliv.
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import (ApoResult, AteResult, CateResult, GateResult, LateResult, PolicyTreeResult, SensitivityResult,
+from .result import (ApoResult, AteResult, CateResult, GateResult, LateResult, PlivResult, PolicyTreeResult, SensitivityResult,
                      TargetResult, format_table, results_frame)
 from .utils import guards
 from .utils.tracing import trace
@@ -490,6 +492,45 @@ def ate_dml_apos(Y, D, X, reference=None, folds=5, seed=1991, lambda_rule="min",
         return DA.dml_apos_lasso(Y, D, X, reference=reference, folds=folds, seed=seed,
                                  lambda_rule=lambda_rule, clip=clip, n_boot=n_boot, level=level,
                                  device=run.device(), dtype=run.dtype)
+
+
+def ate_dml_pliv(Y, D, Z, X, folds=5, seed=1991, lambda_rule="min", clusters=None, run=None,
+                 repeats=1, nuisance="linear", form=None, dist=None,
+                 method="DML-PLIV cross-fit (LASSO)") -> PlivResult:
+    """The effect of a real treatment D (a dose, a price, a number of contacts) with an
+    endogeneity problem, in the cross-fitted partially linear IV model (DoubleML
+    DoubleMLPLIV, partialling-out score) with CV-LASSO nuisances E[Y|X], E[D|X] and E[Z_j|X]:
+    Z is (n,) or (n, q) with 1 <= q <= 4 continuous or discrete instruments
+    (estimators/pliv.py). The result carries theta with its SE and CI, the first-stage weights
+    ``pi``, the homoskedastic first-stage partial F with a ``weak_instruments`` flag (F < 10),
+    ``result.ar_stat(theta)`` and the weak-instrument-robust ``result.anderson_rubin()`` set.
+    ``seed`` keys the folds, which are those of ate_dml; ``run`` picks the backend, device and
+    panel type. ``clusters``: an (n,) vector of labels of dependent rows -- whole clusters are
+    cross-fitted and the SE is cluster-robust, as ate_dml(clusters=).
+    ValueError before any device work: more than 4 instruments, a constant instrument, row
+    shards (``dist``), ``repeats`` other than 1, a logit ``nuisance``, a gate / cate / policy /
+    sensitivity ``form``, more covariates than the pass stages in LDS; after the call:
+    instruments that are collinear once X is partialled out."""
+    run = _run(run)
+    with trace("ate_dml_pliv", folds=folds):
+        from .estimators import pliv as DP
+        DP.check_scope(dist, repeats, nuisance, form)
+        Zn = DP.check_instruments(Z, len(_np(Y)))
+        DP.check_lds(_np(X).shape[1] if _np(X).ndim == 2 else 1, Zn.shape[1], run.dtype)
+        if _ref(run):
+            from .reference import estimators as R
+            codes = None
+            if clusters is not None:
+                from .estimators import cluster as DC
+                codes = DC.cluster_layout(clusters, len(Zn), folds, seed).codes
+            return R.dml_pliv_lasso(Y, D, Zn, X, folds=folds, seed=seed, lambda_rule=lambda_rule,
+                                    method=method, clusters=codes)
+        if clusters is not None:
+            return DP.dml_pliv_lasso_cluster(Y, D, Zn, X, clusters, folds=folds, seed=seed,
+                                             lambda_rule=lambda_rule, method=method,
+                                             device=run.device(), dtype=run.dtype)
+        return DP.dml_pliv_lasso(Y, D, Zn, X, folds=folds, seed=seed, lambda_rule=lambda_rule,
+                                 method=method, device=run.device(), dtype=run.dtype)
 
 
 def ate_residual_balance(Y, W, X, balance: BalanceConfig | None = None,

@@ -3,6 +3,7 @@
   replicate  run the 14-row driver (ate_replication.Rmd) and print/log/plot it
   dml        K-fold DML cross-fit on a synthetic N x p panel (the north-star job)
   late       the LATE of the interactive IV model (DML-IIVM) on a synthetic encouragement design
+  pliv       the partially linear IV model (DML-PLIV) on a synthetic endogenous-dose design
   apos       the mean potential outcomes of a multi-arm treatment (DML-APOS) on a synthetic mailing design
   cluster    cluster-robust DML (PLR or IRM) on synthetic data with a cluster random effect
   build      compile the gfx950 HIP library and the host C++ library
@@ -288,6 +289,29 @@ def _cluster(a):
     return 0
 
 
+def _pliv(a):
+    # the partially linear IV model on the endogenous-dose design of data.dgp, with the truth
+    # and the (biased) partially linear regression beside it
+    import numpy as np
+    from .api import ate_dml, ate_dml_pliv
+    from .config import RunConfig
+    from .data.dgp import make_pliv_data
+    run = RunConfig(backend=a.backend, dtype=a.dtype, seed=a.seed)
+    try:
+        d = make_pliv_data(a.n, a.seed, a.instruments, strength=a.strength)
+        cl = None if a.cluster_size is None else np.arange(d.n) // max(a.cluster_size, 1)
+        r = ate_dml_pliv(d.Y, d.D, d.Z, d.X, folds=a.folds, seed=a.seed,
+                         lambda_rule=a.lambda_rule, clusters=cl, run=run)
+        plr = ate_dml(d.Y, d.D, d.X, folds=a.folds, lambda_rule=a.lambda_rule, run=run)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    out = json.loads(r.json())
+    out["theta_true"] = d.theta_true
+    out["plr"] = {"estimate": plr.ate, "se": plr.se}
+    print(json.dumps(out))
+    return 0
+
+
 def _build(a):
     from . import _build as b
     b.build_all()
@@ -409,6 +433,18 @@ def main(argv=None):
     c.add_argument("--backend", default="auto", choices=["auto", "gpu", "cpu", "reference"])
     c.add_argument("--dtype", default="f64", choices=["f64", "f32", "bf16"])
     c.set_defaults(fn=_cluster)
+    v = sub.add_parser("pliv")
+    v.add_argument("--n", type=int, default=50_000)
+    v.add_argument("--instruments", type=int, default=1, help="instruments of the design (1..4)")
+    v.add_argument("--strength", type=float, default=0.5, help="scale of the first stage")
+    v.add_argument("--seed", type=int, default=1991)
+    v.add_argument("--folds", type=int, default=5)
+    v.add_argument("--cluster-size", type=int, default=None,
+                   help="rows per cluster: cluster-level folds and the cluster-robust SE")
+    v.add_argument("--lambda-rule", default="min", choices=["min", "1se"])
+    v.add_argument("--backend", default="auto", choices=["auto", "gpu", "cpu", "reference"])
+    v.add_argument("--dtype", default="f64", choices=["f64", "f32", "bf16"])
+    v.set_defaults(fn=_pliv)
     b = sub.add_parser("build")
     b.set_defaults(fn=_build)
     a = ap.parse_args(argv)

@@ -374,3 +374,54 @@ def make_clustered_data(n: int = 50_000, cluster_size: int = 5, icc: float = 0.3
     Y = 0.5 * col["yob"] + 0.3 * col["g2000"] + CLUSTER_TAU * W + \
         np.sqrt(icc) * _normal(seed, S_CL_U, cid) + np.sqrt(1.0 - icc) * _normal(seed, S_CL_E, idx)
     return ClusteredData(X=d.X, Y=Y, W=W, clusters=cl, names=list(d.names), tau_true=CLUSTER_TAU)
+
+
+S_PL_Z = 80         # PLIV data: 80..83 the instruments' noise
+S_PL_U = 84         # PLIV data: the unobserved confounder of D and Y
+S_PL_D = 85         # PLIV data: the treatment's own noise
+S_PL_Y = 86         # PLIV data: the outcome's noise
+
+PLIV_THETA = 0.5    # the constant effect of make_pliv_data
+
+
+@dataclass
+class PlivData:
+    X: np.ndarray          # (n, p) float64, the tutorial's covariates
+    Y: np.ndarray          # (n,) float64, continuous
+    D: np.ndarray          # (n,) float64, continuous: the endogenous treatment
+    Z: np.ndarray          # (n, q) float64, continuous instruments
+    names: list
+    theta_true: float
+
+    @property
+    def n(self):
+        return self.X.shape[0]
+
+
+def make_pliv_data(n: int = 50_000, seed: int = 1991, q: int = 1, p_extra: int = 0,
+                   strength: float = 0.5, params: DgpParams = TUTORIAL) -> PlivData:
+    """A continuous treatment with an endogeneity problem on the tutorial's covariates
+    (``make_tutorial_data``): a dose D driven by q instruments (1 <= q <= 4), by X and by a
+    confounder U nobody observes, which also moves the outcome. With e ~ N(0, 1) draws,
+
+        Z_j = 0.4 yob + 0.3 (g2000 - 0.85) (-1)^j + e_j                    j = 0..q-1
+        D   = strength * sum_j Z_j / (1 + j) + 0.5 yob + 0.4 g2002 + U + 0.5 e_D
+        Y   = PLIV_THETA D + 0.5 yob + 0.3 g2000 + U + e_Y
+
+    The instruments depend on X (they are valid only after partialling X out) and reach Y
+    through D alone; cov(D, U) > 0, so the partially linear regression of Y on D is biased
+    upwards by about 1 / (strength^2 sum_j (1 + j)^-2 + 1.25), while PLIV recovers
+    ``theta_true``. ``strength`` scales the first stage (0: irrelevant instruments). Every draw
+    is a Philox function of (seed, stream, row)."""
+    if not 1 <= q <= 4:
+        raise ValueError(f"make_pliv_data draws 1 to 4 instruments, got q = {q}")
+    d = make_tutorial_data(n, seed, p_extra, params)
+    col = {k: d.X[:, j] for j, k in enumerate(d.names)}
+    idx = np.arange(n, dtype=np.uint64)
+    Z = np.column_stack([0.4 * col["yob"] + 0.3 * (col["g2000"] - 0.85) * (-1.0) ** j
+                         + _normal(seed, S_PL_Z + j, idx) for j in range(q)])
+    U = _normal(seed, S_PL_U, idx)
+    D = strength * (Z / (1.0 + np.arange(q))).sum(1) + 0.5 * col["yob"] + 0.4 * col["g2002"] \
+        + U + 0.5 * _normal(seed, S_PL_D, idx)
+    Y = PLIV_THETA * D + 0.5 * col["yob"] + 0.3 * col["g2000"] + U + _normal(seed, S_PL_Y, idx)
+    return PlivData(X=d.X, Y=Y, D=D, Z=Z, names=list(d.names), theta_true=PLIV_THETA)

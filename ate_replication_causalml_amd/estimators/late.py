@@ -26,8 +26,9 @@ r1 = 1. A fixed nuisance is not fitted (K K path problems fewer each) and its co
 is zero (r1: intercept 1).
 
 Out of scope: repeated cross-fitting; group, curve, policy and sensitivity versions of the
-LATE; the partially linear IV model; instruments that are not binary; and an instrument in
-the device data generator (``data.device_dgp``) -- panels come from host arrays
+LATE; instruments or treatments that are not binary (a real treatment with one or several
+real instruments is the partially linear IV model, ``estimators/pliv.py``); and an instrument
+in the device data generator (``data.device_dgp``) -- panels come from host arrays
 (``data.dgp.make_late_data``).
 """
 from __future__ import annotations

@@ -396,6 +396,74 @@ def dml_plr_lasso(Y, W, X, folds=5, seed=1991, lambda_rule="min",
     return AteResult.make(method, r.ate, se, n=len(Y), **_cluster_diag(codes, J, r.se))
 
 
+def _pliv_residuals(Y, D, Z, X, folds, seed, lambda_rule, fold_ids=None):
+    """The held-out residuals (y~ [n], d~ [n], z~ [n, q]) of the cross-fitted partially linear
+    IV model: for held-out fold k, l = E[Y|X], r = E[D|X] and m_j = E[Z_j|X] are gaussian
+    LASSO fits on the other K - 1 folds with lambda chosen by (K-1)-fold CV over those folds
+    (the nuisance code of dml_plr_lasso)."""
+    fid = rng.fold_ids(len(Y), folds, seed, stream=0) if fold_ids is None else \
+        np.asarray(fold_ids, dtype=np.int64)
+    s = "lambda.min" if lambda_rule == "min" else "lambda.1se"
+    targets = np.column_stack([Y, D, Z])
+    res = np.empty_like(targets)
+    for k in range(folds):
+        tr = fid != k
+        te = ~tr
+        inner = fid[tr]
+        inner = np.where(inner > k, inner - 1, inner)
+        for c in range(targets.shape[1]):
+            cv = gn.cv_glmnet(X[tr], targets[tr, c], foldid=inner)
+            res[te, c] = targets[te, c] - cv.predict(X[te], s=s)
+    return res[:, 0], res[:, 1], res[:, 2:]
+
+
+def pliv_moments_from_residuals(yr, dr, zr):
+    """The moment vector of result.PlivLayout from per-row residuals (zr: [n, q])."""
+    from ..result import pliv_layout
+    q = zr.shape[1]
+    w = lambda a, b: (zr * (a * b)[:, None]).T @ zr
+    return pliv_layout(q).pack(len(yr), yr @ yr, yr @ dr, dr @ dr, zr.T @ yr, zr.T @ dr,
+                               zr.T @ zr, w(yr, yr), w(yr, dr), w(dr, dr))
+
+
+def dml_pliv_lasso(Y, D, Z, X, folds=5, seed=1991, lambda_rule="min",
+                   method="DML-PLIV cross-fit (LASSO)", fold_ids=None, clusters=None):
+    """The cross-fitted partially linear IV estimate (Chernozhukov et al. 2018 §4.2, DoubleML
+    DoubleMLPLIV, partialling-out score) with CV-LASSO nuisances, row by row in float64, the
+    twin of estimators.pliv.dml_pliv_lasso: D any real treatment, Z (n,) or (n, q) instruments
+    with 1 <= q <= 4. With the held-out residuals y~, d~, z~: pi = (S z~z~')^-1 S z~d~,
+    v = z~ pi, theta = S v y~ / S v d~, SE = sqrt(S v^2 (y~ - theta d~)^2) / S v d~ -- taken
+    from the moments of result.PlivLayout, summed over the per-row arrays here. ``clusters``:
+    (n,) labels -- whole clusters are cross-fitted (:func:`cluster_fold_ids`) and the SE is
+    the cluster-robust one of psi = v y~ - theta v d~ (:func:`cluster_se`, no correction)."""
+    from ..result import PLIV_MAX_INSTRUMENTS, PlivResult
+    Y, D, X = _arr(Y), _arr(D), _arr(X)
+    Z = _arr(Z)
+    Z = Z[:, None] if Z.ndim == 1 else Z
+    if Z.ndim != 2 or len(Z) != len(Y) or not 1 <= Z.shape[1] <= PLIV_MAX_INSTRUMENTS:
+        raise ValueError(f"Z must be (n,) or (n, q) with 1 <= q <= {PLIV_MAX_INSTRUMENTS}, got "
+                         f"shape {tuple(Z.shape)}")
+    for j in range(Z.shape[1]):
+        if np.ptp(Z[:, j]) == 0.0:
+            raise ValueError(f"instrument {j} is constant: it cannot move the treatment")
+    if clusters is not None:
+        fold_ids = cluster_fold_ids(clusters, folds, seed)
+    yr, dr, zr = _pliv_residuals(Y, D, Z, X, folds, seed, lambda_rule, fold_ids)
+    mom = pliv_moments_from_residuals(yr, dr, zr)
+    r = PlivResult.from_moments(method, mom, n=len(Y), hipgraph=False)
+    if r.rank_deficient:
+        raise ValueError(f"the {Z.shape[1]} instrument residuals are collinear after "
+                         "partialling out X")
+    if clusters is None:
+        return r
+    codes, J = cluster_codes(clusters)
+    v = zr @ np.asarray(r.pi)
+    se = cluster_se(v * yr, v * dr, r.theta, codes, correction=False)
+    diag = _cluster_diag(codes, J, r.se)
+    diag.pop("se_unclustered")
+    return PlivResult.from_moments(method, mom, se=se, n=len(Y), hipgraph=False, **diag)
+
+
 PROPENSITIES = ("linear", "logit")
 
 

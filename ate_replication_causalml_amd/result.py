@@ -1287,6 +1287,382 @@ class ApoResult:
     to_json = json
 
 
+# ------------------------------------------------- partially linear IV model (DML-PLIV)
+PLIV_MAX_INSTRUMENTS = 4
+PLIV_RANK_TOL = 1e-12   # a Cholesky pivot of S z~z~' at or below this times its largest diagonal
+
+
+@dataclass(frozen=True)
+class PlivLayout:
+    """Where the moments of the PLIV pass live for q instruments (the host twin of
+    csrc/pliv.hip ``pliv_n`` and its header), with y~, d~, z~ the held-out residuals and
+    T = q (q + 1) / 2: ``n`` at 0, S y~y~, S y~d~, S d~d~ at 1..3, S z~_i y~ at ``zy + i``,
+    S z~_i d~ at ``zd + i``, S z~_i z~_j (i <= j) at ``zz + tri(i, j)`` and the fourth moments
+    Q_yy, Q_yd, Q_dd = S z~_i z~_j {y~y~, y~d~, d~d~} at ``qyy`` / ``qyd`` / ``qdd + tri(i, j)``.
+    ``size``: 10 / 20 / 34 / 52 for q = 1..4."""
+    q: int
+
+    def __post_init__(self):
+        if not 1 <= self.q <= PLIV_MAX_INSTRUMENTS:
+            raise ValueError(f"DML-PLIV takes 1 to {PLIV_MAX_INSTRUMENTS} instruments, got "
+                             f"{self.q}")
+
+    @property
+    def T(self) -> int:
+        return self.q * (self.q + 1) // 2
+
+    @property
+    def zy(self) -> int:
+        return 4
+
+    @property
+    def zd(self) -> int:
+        return 4 + self.q
+
+    @property
+    def zz(self) -> int:
+        return 4 + 2 * self.q
+
+    @property
+    def qyy(self) -> int:
+        return self.zz + self.T
+
+    @property
+    def qyd(self) -> int:
+        return self.zz + 2 * self.T
+
+    @property
+    def qdd(self) -> int:
+        return self.zz + 3 * self.T
+
+    @property
+    def size(self) -> int:
+        return self.zz + 4 * self.T
+
+    def tri(self, i: int, j: int) -> int:
+        """The offset of entry (i, j): row-major over the upper triangle."""
+        i, j = (i, j) if i <= j else (j, i)
+        return i * self.q - i * (i - 1) // 2 + (j - i)
+
+    def names(self) -> list:
+        q = self.q
+        pairs = [(i, j) for i in range(q) for j in range(i, q)]
+        return (["n", "S yy", "S yd", "S dd"] + [f"S z{i} y" for i in range(q)] +
+                [f"S z{i} d" for i in range(q)] + [f"S z{i} z{j}" for i, j in pairs] +
+                [f"S z{i} z{j} {t}" for t in ("yy", "yd", "dd") for i, j in pairs])
+
+    def pack(self, n, syy, syd, sdd, szy, szd, szz, qyy, qyd, qdd) -> list:
+        """The moment vector from its parts (szz, qyy, qyd, qdd: q x q symmetric)."""
+        q = self.q
+        pairs = [(i, j) for i in range(q) for j in range(i, q)]
+        return ([float(n), float(syy), float(syd), float(sdd)] + [float(v) for v in szy] +
+                [float(v) for v in szd] +
+                [float(M[i][j]) for M in (szz, qyy, qyd, qdd) for i, j in pairs])
+
+    def unpack(self, mom) -> dict:
+        """The parts of a moment vector: n, syy, syd, sdd, szy [q], szd [q] and the full
+        symmetric q x q lists szz, qyy, qyd, qdd."""
+        m = [float(v) for v in mom]
+        if len(m) != self.size:
+            raise ValueError(f"{self.size} moments expected at q = {self.q}, got {len(m)}")
+        q = self.q
+        sym = lambda o: [[m[o + self.tri(i, j)] for j in range(q)] for i in range(q)]
+        return dict(n=m[0], syy=m[1], syd=m[2], sdd=m[3], szy=m[self.zy:self.zy + q],
+                    szd=m[self.zd:self.zd + q], szz=sym(self.zz), qyy=sym(self.qyy),
+                    qyd=sym(self.qyd), qdd=sym(self.qdd))
+
+
+def pliv_layout(q: int) -> PlivLayout:
+    return PlivLayout(int(q))
+
+
+def pliv_instruments_of(n_moments: int) -> int:
+    """q from the length of a moment vector."""
+    for q in range(1, PLIV_MAX_INSTRUMENTS + 1):
+        if PlivLayout(q).size == n_moments:
+            return q
+    raise ValueError(f"{n_moments} is not the moment count of any number of instruments in "
+                     f"1..{PLIV_MAX_INSTRUMENTS}")
+
+
+def _chol_solve_small(A, b, tol=0.0):
+    """x with A x = b for a small symmetric positive definite A (lists) by Cholesky, in the
+    operation order of csrc/pliv.hip ``pliv_finish_kernel``; None when a pivot is at or below
+    ``tol`` times the largest diagonal entry."""
+    k = len(A)
+    dmax = max([0.0] + [A[i][i] for i in range(k)])
+    if not dmax > 0.0:
+        return None
+    L = [[0.0] * k for _ in range(k)]
+    for j in range(k):
+        d = A[j][j]
+        for c in range(j):
+            d -= L[j][c] * L[j][c]
+        if not d > tol * dmax:
+            return None
+        L[j][j] = math.sqrt(d)
+        for i in range(j + 1, k):
+            t = A[i][j]
+            for c in range(j):
+                t -= L[i][c] * L[j][c]
+            L[i][j] = t / L[j][j]
+    f = [0.0] * k
+    for i in range(k):
+        t = b[i]
+        for c in range(i):
+            t -= L[i][c] * f[c]
+        f[i] = t / L[i][i]
+    x = [0.0] * k
+    for i in range(k - 1, -1, -1):
+        t = f[i]
+        for c in range(i + 1, k):
+            t -= L[c][i] * x[c]
+        x[i] = t / L[i][i]
+    return x
+
+
+def pliv_finish(mom) -> list:
+    """[theta, SE, pi' S z~d~, rank flag, pi_1..pi_q] from the PLIV moments, float64 on the
+    host: the twin of the in-kernel finish of csrc/pliv.hip, operation by operation.
+
+        pi    = (S z~z~')^-1 S z~d~                 (Cholesky; no intercept)
+        theta = pi' S z~y~ / pi' S z~d~
+        Omega = Q_yy - 2 theta Q_yd + theta^2 Q_dd
+        SE    = sqrt(pi' Omega pi) / (pi' S z~d~)
+
+    A pivot at or below PLIV_RANK_TOL times the largest diagonal entry of S z~z~' sets the
+    flag (1.0) and makes every other entry NaN."""
+    lay = PlivLayout(pliv_instruments_of(len(mom)))
+    u = lay.unpack(mom)
+    q = lay.q
+    nan = float("nan")
+    pi = _chol_solve_small(u["szz"], u["szd"], PLIV_RANK_TOL)
+    if pi is None:
+        return [nan, nan, nan, 1.0] + [nan] * q
+    num = den = 0.0
+    for i in range(q):
+        num += pi[i] * u["szy"][i]
+        den += pi[i] * u["szd"][i]
+    # IEEE division, as on the device: x / 0 is an infinity or NaN, not an exception
+    div = lambda a, b: a / b if b != 0.0 else (nan if a == 0.0 or a != a else math.copysign(
+        float("inf"), a) * math.copysign(1.0, b))
+    th = div(num, den)
+    var = 0.0
+    for i in range(q):
+        for j in range(q):
+            var += pi[i] * pi[j] * (u["qyy"][i][j] - 2.0 * th * u["qyd"][i][j]
+                                    + th * th * u["qdd"][i][j])
+    return [th, div(math.sqrt(var if var > 0.0 else 0.0), den), den, 0.0] + pi
+
+
+def chi2_quantile(level: float, df: int) -> float:
+    """x with P(chi2_df <= x) = level, by bisection of ``_chi2_sf`` (df = 1: the squared
+    normal quantile of ``LateResult.anderson_rubin``)."""
+    if not 0.0 < level < 1.0:
+        raise ValueError("level must be in (0, 1)")
+    if df == 1:
+        return normal_quantile(0.5 + level / 2.0) ** 2
+    lo, hi = 0.0, 1.0
+    while _chi2_sf(hi, df) > 1.0 - level:
+        hi *= 2.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if _chi2_sf(mid, df) > 1.0 - level:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+@dataclass
+class ArGridSet:
+    """The Anderson-Rubin set of a PLIV fit with several instruments, on a grid of theta:
+    ``inside[i]`` says whether ``grid[i]`` is accepted; lower / upper are the extreme accepted
+    points (NaN when none is). kind "empty", "interval" (the accepted points are consecutive)
+    or "union"; ``open_ended`` when an end point of the grid is accepted, so the set may go on
+    beyond it."""
+    kind: str
+    lower: float
+    upper: float
+    level: float
+    grid: list
+    inside: list
+    open_ended: bool
+
+    def __contains__(self, theta) -> bool:
+        if self.kind == "empty":
+            return False
+        near = min(range(len(self.grid)), key=lambda i: abs(self.grid[i] - theta))
+        return bool(self.inside[near])
+
+
+@dataclass
+class PlivResult:
+    """The effect of a real treatment D in the cross-fitted partially linear IV model
+    (DoubleML ``DoubleMLPLIV``, partialling-out score) with q instruments: ``theta`` with its
+    SE and CI, the first-stage weights ``pi`` of the instrument residuals, the homoskedastic
+    first-stage partial F and the ``weak_instruments`` flag (F < 10). Everything is a host
+    function of ``moments`` (PlivLayout); a cluster-robust fit replaces the SE
+    (``from_moments(se=)``) and keeps the unclustered one in the diagnostics."""
+    method: str
+    theta: float
+    se: float
+    lower_ci: float
+    upper_ci: float
+    pi: list
+    first_stage_F: float
+    weak_instruments: bool
+    rank_deficient: bool
+    moments: list
+    diagnostics: dict = field(default_factory=dict)
+
+    @classmethod
+    def from_moments(cls, method, mom, se=None, **diag):
+        """From the moments; n_instruments and the held-out RMSE of l and r come from them
+        too, ``diag`` adds n and hipgraph. se: a standard error that replaces the score's
+        (the cluster-robust one); the score's goes to diagnostics["se_unclustered"] then."""
+        mom = [float(v) for v in mom]
+        lay = PlivLayout(pliv_instruments_of(len(mom)))
+        q = lay.q
+        fin = pliv_finish(mom)
+        th, se0, den, flag = fin[:4]
+        pi = fin[4:]
+        n, syy, sdd = mom[0], mom[1], mom[3]
+        rss = sdd - den
+        F = (den / q) / (rss / (n - q)) if flag == 0.0 and rss > 0 and n > q else float("nan")
+        rm = lambda s: math.sqrt(s / n) if n > 0 and s >= 0 else float("nan")
+        d = dict(n_instruments=q, rmse_l=rm(syy), rmse_r=rm(sdd))
+        if se is not None:
+            d["se_unclustered"] = se0
+        d.update(diag)
+        d.setdefault("n", int(round(n)) if math.isfinite(n) else -1)
+        s = se0 if se is None else float(se)
+        return cls(method, th, s, th - Z * s, th + Z * s, pi, F, bool(F < 10.0), flag != 0.0,
+                   mom, d)
+
+    @property
+    def layout(self) -> PlivLayout:
+        return PlivLayout(pliv_instruments_of(len(self.moments)))
+
+    # the record of every estimator table (AteResult.row)
+    @property
+    def ate(self) -> float:
+        return self.theta
+
+    def row(self):
+        return {"Method": self.method, "ATE": self.theta, "lower_ci": self.lower_ci,
+                "upper_ci": self.upper_ci, "se": self.se}
+
+    def _g_omega(self, theta):
+        u = self.layout.unpack(self.moments)
+        q = self.layout.q
+        g = [u["szy"][i] - theta * u["szd"][i] for i in range(q)]
+        om = [[u["qyy"][i][j] - 2.0 * theta * u["qyd"][i][j] + theta * theta * u["qdd"][i][j]
+               for j in range(q)] for i in range(q)]
+        return g, om
+
+    def ar_stat(self, theta) -> float:
+        """The Anderson-Rubin statistic g' Omega(theta)^-1 g with g = S z~y~ - theta S z~d~
+        and Omega(theta) = Q_yy - 2 theta Q_yd + theta^2 Q_dd: chi2 with q degrees of freedom
+        under H0: theta_0 = theta, however weak the instruments. NaN when Omega(theta) is not
+        positive definite."""
+        g, om = self._g_omega(float(theta))
+        x = _chol_solve_small(om, g, 0.0)
+        if x is None:
+            return float("nan")
+        return sum(a * b for a, b in zip(g, x))
+
+    def anderson_rubin(self, level=0.95, grid=None):
+        """The weak-instrument-robust confidence set {theta : ar_stat(theta) <=
+        chi2_q(level)}. q = 1: in closed form, the quadratic inequality A theta^2 + B theta +
+        C <= 0 with c = chi2_1(level),
+
+            A = (S z~d~)^2 - c Q_dd     B = -2 S z~y~ S z~d~ + 2 c Q_yd     C = (S z~y~)^2 - c Q_yy
+
+        and the cases of ``LateResult.anderson_rubin`` (A > 0: an interval; A < 0: two rays,
+        or the whole line without a real root) -> ``ArSet``. q > 1: over ``grid`` (default:
+        401 points over theta +- 10 SE) -> ``ArGridSet``."""
+        crit = chi2_quantile(level, self.layout.q)
+        if self.layout.q == 1:
+            u = self.layout.unpack(self.moments)
+            sy, sd = u["szy"][0], u["szd"][0]
+            qyy, qyd, qdd = u["qyy"][0][0], u["qyd"][0][0], u["qdd"][0][0]
+            inf = float("inf")
+            A = sd * sd - crit * qdd
+            B = -2.0 * sy * sd + 2.0 * crit * qyd
+            C = sy * sy - crit * qyy
+            if A == 0.0:                                    # B theta + C <= 0
+                if B == 0.0:
+                    return ArSet("all", -inf, inf, level)
+                return ArSet("two_rays", -C / B, inf, level) if B > 0 else \
+                    ArSet("two_rays", -inf, -C / B, level)
+            disc = B * B - 4 * A * C
+            if disc <= 0.0 and A < 0:
+                return ArSet("all", -inf, inf, level)
+            r = math.sqrt(max(disc, 0.0))
+            qq = -0.5 * (B + math.copysign(r, B))
+            roots = sorted((qq / A, C / qq)) if qq != 0.0 else [0.0, 0.0]
+            return ArSet("interval" if A > 0 else "two_rays", roots[0], roots[1], level)
+        if grid is None:
+            if not (math.isfinite(self.theta) and math.isfinite(self.se) and self.se > 0):
+                raise ValueError("a grid= of theta values is needed: theta or SE is not finite")
+            grid = [self.theta + self.se * (k - 200) / 20.0 for k in range(401)]
+        grid = sorted(float(t) for t in grid)
+        if not grid:
+            raise ValueError("grid must hold at least one theta")
+        inside = [bool(self.ar_stat(t) <= crit) for t in grid]
+        hit = [i for i, v in enumerate(inside) if v]
+        if not hit:
+            return ArGridSet("empty", float("nan"), float("nan"), level, grid, inside, False)
+        kind = "interval" if hit[-1] - hit[0] + 1 == len(hit) else "union"
+        return ArGridSet(kind, grid[hit[0]], grid[hit[-1]], level, grid, inside,
+                         inside[0] or inside[-1])
+
+    def _ar_text(self, ar) -> str:
+        if isinstance(ar, ArGridSet):
+            if ar.kind == "empty":
+                return "empty on the grid"
+            tail = " (reaches the end of the grid)" if ar.open_ended else ""
+            return f"{ar.kind} within [{ar.lower:.4f}, {ar.upper:.4f}]{tail}"
+        return {"interval": f"[{ar.lower:.4f}, {ar.upper:.4f}]", "all": "the whole line",
+                "two_rays": f"(-inf, {ar.lower:.4f}] and [{ar.upper:.4f}, inf)"}[ar.kind]
+
+    def table(self) -> str:
+        d = self.diagnostics
+        lines = [
+            f"{self.method}: n {d.get('n', '?')}, instruments {self.layout.q}, first-stage F "
+            f"{self.first_stage_F:.2f}{' (WEAK: F < 10)' if self.weak_instruments else ''}, "
+            f"rmse l {d.get('rmse_l', float('nan')):.4f} r {d.get('rmse_r', float('nan')):.4f}",
+            f"{'':>12s} {'effect':>9s} {'SE':>9s} {'lower_ci':>9s} {'upper_ci':>9s}",
+            f"{'theta':>12s} {self.theta:9.4f} {self.se:9.4f} {self.lower_ci:9.4f} "
+            f"{self.upper_ci:9.4f}",
+            "pi: " + " ".join(f"{v:.4f}" for v in self.pi)]
+        if "n_clusters" in d:
+            lines.append(f"clusters {d['n_clusters']}, largest {d.get('max_cluster', '?')}, "
+                         f"unclustered SE {d.get('se_unclustered', float('nan')):.4f}")
+        if not self.rank_deficient:
+            lines.append(f"Anderson-Rubin 95% set: {self._ar_text(self.anderson_rubin())}")
+        return "\n".join(lines)
+
+    def json(self) -> str:
+        keep = lambda d: {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v))
+                          for k, v in d.items()}
+        out = {"method": self.method, "theta": self.theta, "se": self.se,
+               "lower_ci": self.lower_ci, "upper_ci": self.upper_ci, "pi": self.pi,
+               "first_stage_F": self.first_stage_F, "weak_instruments": self.weak_instruments,
+               "rank_deficient": self.rank_deficient, "moments": self.moments,
+               "diagnostics": keep(self.diagnostics)}
+        if not self.rank_deficient:
+            ar = self.anderson_rubin()
+            a = asdict(ar)
+            a.pop("grid", None)
+            a.pop("inside", None)
+            out["anderson_rubin"] = a
+        return json.dumps(out)
+
+    to_json = json
+
+
 def results_frame(results):
     import pandas as pd
     return pd.DataFrame([r.row() for r in results])

@@ -53,6 +53,15 @@ launches with their glue) on the call's Gram stack, and the potential-outcome pa
 with it in the same process, and the JSON line says whether the shared sums have the same
 bits. Recorded in profiles/apos/README.md.
 
+``--pliv q``: the partially linear IV model with q instruments (``estimators/pliv.py``) beside
+PLR on the same plain K-fold panel (the covariates x0..x{q-1} are the instruments and leave the
+covariates; the panel's W is the treatment): one captured ``pliv_phases`` call and one captured
+``dml_phases`` call, alternated; the PLIV fit phase alone (its path launch or launches); then
+the PLIV pass (``ate_pliv_moments``, its finishing launch included) and PLR's 7-moment pass
+(``ate_dml_resid_moments``) with the picked coefficients, in batches as for ``--targets``. The
+JSON line carries the pass's byte model (rows x (union of supports + 2 (2 + q) + 1 target and
+valid columns) x element size) and its rate. Recorded in profiles/pliv/README.md.
+
 ``--clusters``: the cluster-robust call (``estimators/cluster.py``) beside the plain ATE on the
 same arm-split panel, for four cluster-size profiles over the panel's real rows (singletons,
 households of 1-6, 50 equal clusters, one cluster of half the rows plus singletons; clusters
@@ -97,6 +106,8 @@ def main():
                     help="--iivm: the exactly-binary covariate x{J} taken as the treatment D")
     ap.add_argument("--apos", type=int, default=0, metavar="L",
                     help="time the potential outcomes of an L-arm treatment (2..8)")
+    ap.add_argument("--pliv", type=int, default=0, metavar="q",
+                    help="time the partially linear IV model with q instruments (1..4)")
     ap.add_argument("--propensity", default="linear", choices=["linear", "logit"],
                     help="logit: time the binomial CV-LASSO propensity beside the linear one")
     ap.add_argument("--clusters", action="store_true",
@@ -115,6 +126,8 @@ def main():
     kw = dict(p=a.p, folds=K, seed=a.seed, dtype=a.dtype, device=dev, blocked=blocked, dgp=a.dgp)
     if a.apos:
         return apos(a, n, K)
+    if a.pliv:
+        return pliv(a, n, K, kw)
     if a.clusters:
         return clusters(a, n, K, kw)
     if a.repeats > 0:
@@ -724,6 +737,101 @@ def apos(a, n, K):
     out["apo_true"] = [float(v) for v in d.apo_true]
     out["contrasts"] = [(c.effect, c.se) for c in r.contrasts()]
     out["crit"] = r.crit
+    print(json.dumps(out))
+
+
+def pliv(a, n, K, kw):
+    import dataclasses
+    import numpy as np
+    import torch
+    from ate_replication_causalml_amd.data.device_dgp import synthetic_panel
+    from ate_replication_causalml_amd.estimators import lasso as DL
+    from ate_replication_causalml_amd.estimators import pliv as DP
+    from ate_replication_causalml_amd.ops.gram import plan_slot
+    from ate_replication_causalml_amd.result import PlivResult, pliv_layout
+    from ate_replication_causalml_amd.utils.graphs import SegmentedStep
+    q = a.pliv
+    plain = synthetic_panel(n, **kw)
+    torch.cuda.synchronize()
+    # the covariates x0..x{q-1} (continuous) are the instruments and leave the covariates. A
+    # bf16 covariate is its own hi part; its lo part is W's, which is all zero (W is binary).
+    cols = dict(plain.cols)
+    zc = [plain.cols[f"x{j}"] for j in range(q)]
+    for j, c in enumerate(zc):
+        cols[f"Z{j}"] = c
+        if plain.dtype == torch.bfloat16:
+            cols.update({f"Z{j}_hi": c, f"Z{j}_lo": plain.cols["W_lo"]})
+    pan = dataclasses.replace(plain, cols=cols, xcols=[x for x in plain.xcols if x not in zc])
+    rows = np.asarray(plain.seg_nreal, dtype=np.float64)
+    esz = plain.data.element_size()
+
+    def nbytes(coef, ntarget):
+        nnz = (coef[:, :, 1:] != 0).any(1).sum(1).cpu().numpy()
+        return nnz.tolist(), int((rows * (nnz + ntarget) * esz).sum())
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = f()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    with plan_slot(0):
+        plr = SegmentedStep(DL.dml_phases(plain, K, "min"), graph=True, warmup=1)
+    with plan_slot(1):
+        piv = SegmentedStep(DP.pliv_phases(pan, K, q, "min"), graph=True, warmup=1)
+    for _ in range(a.warmup):
+        plr()
+        st = piv()
+    torch.cuda.synchronize()
+    coef, G = st["coef"].clone(), st["G"].clone()
+    cv = plr()["cv"]
+    c2 = cv.coef_min.reshape(K, 2, -1).double().contiguous().clone()
+    fit_phase = DP.pliv_fit_phases(pan, K, q, "min")[-1]
+    nb = max(a.pass_batch, 1)
+
+    def batch(f, *args, **kws):
+        def g():
+            for _ in range(nb):
+                out = f(*args, **kws)
+            return out
+        return g
+
+    p_piv = batch(DP.pliv_moments, pan, coef, q, finish=True)
+    p_plr = batch(DL.dml_residual_moments, plain, c2)
+    for _ in range(a.warmup):
+        fit_phase({"G": G})
+        p_piv()
+        p_plr()
+    torch.cuda.synchronize()
+    ms = {"plr_call": [], "pliv_call": [], "pliv_fit": [], "pass7": [], "pass_pliv": []}
+    for _ in range(a.calls):                      # alternate: all see the same clocks
+        ms["plr_call"].append(timed(plr)[0])
+        ms["pliv_call"].append(timed(piv)[0])
+        ms["pliv_fit"].append(timed(lambda: fit_phase({"G": G}))[0])
+        ms["pass7"].append(timed(p_plr)[0] / nb)
+        ms["pass_pliv"].append(timed(p_piv)[0] / nb)
+    split = plain.dtype == torch.bfloat16
+    out = {"mode": "pliv", "instruments": q, "n": n, "p": len(pan.xcols), "folds": K,
+           "dtype": a.dtype, "blocked": kw["blocked"], "dgp": a.dgp, "calls": a.calls,
+           "pass_batch": nb, "graphed": [plr.graphed, piv.graphed],
+           "path_launches": len(DP.path_launches((2 + q) * K, K)), "moments": pliv_layout(q).size,
+           "nbx_pliv": DP.default_nbx(pan, q)}
+    for name, v in ms.items():
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "mean_ms": statistics.fmean(v), "spread_ms": max(v) - min(v)}
+    # target and valid columns per row: one, and Y, D, Z.. once each (hi + lo pairs on bf16)
+    out["union7"], out["bytes7"] = nbytes(c2, 5 if split else 3)
+    out["union_pliv"], out["bytes_pliv"] = nbytes(coef, (2 * (2 + q) if split else 2 + q) + 1)
+    for k, b in (("pass7", "bytes7"), ("pass_pliv", "bytes_pliv")):
+        out[k]["TB_per_s"] = out[b] / (out[k]["median_ms"] * 1e-3) / 1e12
+    out["ratio_pass_pliv_over_pass7"] = out["pass_pliv"]["median_ms"] / out["pass7"]["median_ms"]
+    st = piv()
+    r = PlivResult.from_moments("pliv", st["mom"].cpu().numpy())
+    out["pliv"] = {"theta": r.theta, "se": r.se, "pi": r.pi, "F": r.first_stage_F,
+                   "res": st["res"].cpu().tolist()}
+    out["plr_res"] = plr()["res"].cpu().tolist()
     print(json.dumps(out))
 
 
