@@ -66,6 +66,7 @@ c_double = ctypes.c_double
 _SIGS = {
     "ate_gram_bf16": "pliipipipipppp",
     "ate_gram_bf16_pair": "pllipippipippippiip",
+    "ate_gram_bf16_pair_bits": "pllipippipippippiip",
     "ate_last_error": "pi",
     "ate_last_stale_error": "pi",
     "ate_clear_errors": "",
@@ -129,6 +130,7 @@ _SIGS = {
     "ate_lognet_path_groups": "iplpiipipipppdpdiippppppppp",
     "ate_lognet_cvloss_set": "iplpiipipipppipp",
     "ate_dgp_fill": "iplllllp" + "uiipppp",
+    "ate_dgp_pack_bits": "plpp",
     "ate_sel_block_rows": "",
     "ate_sel_gen_count": "upilllpp",
     "ate_sel_gen_flags": "upillpp",

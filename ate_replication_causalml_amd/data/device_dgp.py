@@ -63,6 +63,63 @@ def fold_slices(n_total: int, folds: int, rank: int = 0, world: int = 1, align: 
 # same bits). ATE_PANEL_BYTES=0: the generator's column order, no byte copy.
 BYTE_COL0 = 384
 BYTE_PANEL = os.environ.get("ATE_PANEL_BYTES", "1") == "1"
+# Bit columns: such a panel also keeps those 128 columns as bits (DevicePanel.bits1, 1 KB per
+# 64-row block, packed once from bytes8 by csrc/dgp.hip ate_dgp_pack_bits); the Gram then
+# streams 784 bytes per row, the same bits. ATE_PANEL_BITS=0: no bit image, the byte path.
+BIT_PANEL = os.environ.get("ATE_PANEL_BITS", "1") == "1"
+BITS_BLOCK = 1024          # bytes of bits1 per 64-row block: 128 columns x 64 rows / 8
+
+
+def bits1_index(col, row):
+    """Host twin of the bit order of ``DevicePanel.bits1`` (csrc/dgp.hip x1_byte / x1_bit):
+    (byte offset within the 1 KB block, bit within that byte) of bit column ``col`` (0..127 =
+    physical column 384 + col) at row ``row`` (0..63) of a 64-row block; numpy arrays
+    broadcast. MFMA lane l = 16 ((row >> 3) & 3) + (col & 15) owns 8 bytes of each 64-column
+    plane: one halfword per 16-column block, even rows in its low byte and odd rows in its
+    high byte, bit 4 (row >> 5) + ((row >> 1) & 3)."""
+    col, row = np.broadcast_arrays(np.asarray(col), np.asarray(row))
+    lane = ((row >> 3) & 3) * 16 + (col & 15)
+    byte = (col >> 6) * 512 + lane * 8 + ((col >> 4) & 3) * 2 + (row & 1)
+    bit = (row >> 5) * 4 + ((row >> 1) & 3)
+    return byte, bit
+
+
+def pack_bits_block(block) -> np.ndarray:
+    """[128 columns, 64 rows] of zero / non-zero -> the block's 1 KB bit image (uint8)."""
+    b = np.asarray(block) != 0
+    if b.shape != (128, 64):
+        raise ValueError("a bit block is 128 columns x 64 rows")
+    byte, bit = bits1_index(np.arange(128)[:, None], np.arange(64)[None, :])
+    out = np.zeros(BITS_BLOCK, dtype=np.uint8)
+    np.bitwise_or.at(out, byte[b], (1 << bit[b]).astype(np.uint8))
+    return out
+
+
+def unpack_bits_block(image) -> np.ndarray:
+    """The inverse: a 1 KB bit image -> [128 columns, 64 rows] of 0 / 1 (uint8)."""
+    im = np.asarray(image, dtype=np.uint8).reshape(BITS_BLOCK)
+    byte, bit = bits1_index(np.arange(128)[:, None], np.arange(64)[None, :])
+    return (im[byte] >> bit.astype(np.uint8)) & 1
+
+
+def pack_bits(bytes8: torch.Tensor) -> torch.Tensor:
+    """The bit image [nblk, 1024] (uint8) of a panel's one-byte columns ``bytes8``
+    [nblk, 128, 64] on the GPU (csrc/dgp.hip ate_dgp_pack_bits), on the current stream."""
+    if not bytes8.is_cuda or not bytes8.is_contiguous() or tuple(bytes8.shape[1:]) != (128, 64):
+        raise ValueError("pack_bits needs a contiguous [nblk, 128, 64] uint8 tensor on the GPU")
+    out = torch.empty((bytes8.shape[0], BITS_BLOCK), dtype=torch.uint8, device=bytes8.device)
+    _native.call("ate_dgp_pack_bits", bytes8.data_ptr(), bytes8.shape[0], out.data_ptr(),
+                 torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def unpack_bits(bits1: torch.Tensor) -> torch.Tensor:
+    """``DevicePanel.bits1`` [nblk, 1024] -> [nblk, 128 columns, 64 rows] of 0 / 1 (uint8),
+    on the tensor's device."""
+    byte, bit = bits1_index(np.arange(128)[:, None], np.arange(64)[None, :])
+    byte = torch.from_numpy(byte.reshape(-1).astype(np.int64)).to(bits1.device)
+    bit = torch.from_numpy(bit.reshape(-1).astype(np.uint8)).to(bits1.device)
+    return ((bits1[:, byte] >> bit) & 1).reshape(-1, 128, 64)
 
 
 def _binary_names(p: int) -> set:
@@ -195,6 +252,8 @@ def synthetic_panel(n_total: int, p: int = 500, folds: int = 5, seed: int = 1991
                          *pan.strides(), int(r0), cnt, g0, gp, seed, p_extra, int(hi_lo),
                          pblk.ctypes.data, None if pcol is None else pcol.data_ptr(),
                          None if pcol is None else pan.bytes8.data_ptr(), s)
+        if pcol is not None and BIT_PANEL:
+            pan.bits1 = pack_bits(pan.bytes8)
     else:
         cm = torch.zeros((pan.P, pan.ld), dtype=pan.data.dtype) if blocked else pan.data
         for k, ((g0, cnt), (r0, _)) in enumerate(zip(slices, pan.seg_bounds)):

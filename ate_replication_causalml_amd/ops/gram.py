@@ -32,7 +32,9 @@ PAIR_SLOTS = 272
 # Panels that carry one-byte copies of their {0, 1} columns (DevicePanel.bytes8: physical
 # columns 384..511 of a P = 512 blocked bf16 panel) stream those to the paired-tile Gram as
 # bytes (csrc/gram.hip): 896 instead of 1,024 bytes per row, the same Gram bits.
-# ATE_GRAM_BYTES=0 reads them as bf16 (A/B).
+# Panels that also carry the bit image of those columns (DevicePanel.bits1) stream that
+# instead: 784 bytes per row, again the same Gram bits. ATE_GRAM_BYTES=0 reads the columns
+# as bf16 (A/B); ATE_PANEL_BITS=0 builds panels without the bit image (the byte path).
 BYTE_COLS = os.environ.get("ATE_GRAM_BYTES", "1") == "1"
 # K-loop schedule of the paired-tile kernel (csrc/gram.hip SCHED_*): "lockstep" (all eight
 # waves run one program, one barrier per 64-row stage) or "stagger" (waves 4-7 run half a
@@ -330,11 +332,14 @@ def gram(panel: DevicePanel, w: torch.Tensor | None = None, done: torch.Tensor |
     s = _stream()
     if X.dtype == torch.bfloat16 and pl.pair:
         cs, bs = panel.strides()
-        x8 = getattr(panel, "bytes8", None)
-        _native.call("ate_gram_bf16_pair", X.data_ptr(), cs, bs, panel.P, pl.tiles.data_ptr(),
+        x8 = getattr(panel, "bytes8", None) if BYTE_COLS else None
+        x1 = getattr(panel, "bits1", None) if x8 is not None else None
+        _native.call("ate_gram_bf16_pair" if x1 is None else "ate_gram_bf16_pair_bits",
+                     X.data_ptr(), cs, bs, panel.P, pl.tiles.data_ptr(),
                      pl.ntiles, pl.blocks.data_ptr(), pl.chunks.data_ptr(), pl.nchunks,
                      pl.seg_chunk0.data_ptr(), panel.nseg, pl.slab.data_ptr(), G.data_ptr(),
-                     _STAGES[stage], Gx, None if x8 is None or not BYTE_COLS else x8.data_ptr(),
+                     _STAGES[stage], Gx,
+                     x1.data_ptr() if x1 is not None else None if x8 is None else x8.data_ptr(),
                      _sched_for(cs), GRAM_PRIO, s)
         return pl.Gx if exact else G
     if stage == "reduce":

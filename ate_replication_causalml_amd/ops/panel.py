@@ -54,6 +54,10 @@ class DevicePanel:
     # blocked bf16 panels from data/device_dgp.synthetic_panel): [ld/64, 128, 64] uint8, 0x3F
     # for 1; the paired-tile Gram streams it instead of those bf16 columns (csrc/gram.hip)
     bytes8: torch.Tensor | None = None
+    # the same columns as bits, packed once from bytes8: [ld/64, 1024] uint8, 1 KB per 64-row
+    # block in the order of data/device_dgp.bits1_index; the paired-tile Gram streams it in
+    # place of bytes8 (784 instead of 896 bytes per row). None: the byte path.
+    bits1: torch.Tensor | None = None
 
     @property
     def P(self):

@@ -262,7 +262,8 @@ def layout_key(*inputs):
         if not isinstance(x, torch.Tensor):
             k += (x.n, tuple(sorted(x.cols.items())), tuple(map(tuple, x.seg_bounds)),
                   tuple(int(c) for c in x.seg_nreal), bool(getattr(x, "identity", False)),
-                  getattr(x, "bytes8", None) is not None)
+                  getattr(x, "bytes8", None) is not None,
+                  getattr(x, "bits1", None) is not None)
         key.append(k)
     return tuple(key)
 
@@ -283,6 +284,8 @@ class _Captured:
                 _data(s).copy_(_data(x))
                 if getattr(x, "bytes8", None) is not None:      # a panel's one-byte columns
                     s.bytes8.copy_(x.bytes8)
+                if getattr(x, "bits1", None) is not None:       # ... and their bit image
+                    s.bits1.copy_(x.bits1)
 
     def __call__(self, inputs):
         self.load(inputs)
@@ -387,6 +390,8 @@ class GraphCache:
                         _data(s).copy_(_data(x))
                         if getattr(x, "bytes8", None) is not None:
                             s.bytes8.copy_(x.bytes8)
+                        if getattr(x, "bits1", None) is not None:
+                            s.bits1.copy_(x.bits1)
                 g = _Captured(body, static, static_args, warmup=1)
             except Exception as e:  # noqa: BLE001 - fall back to eager, but say why
                 print(f"[graphs] {name}: capture failed, running eagerly: {e}", flush=True)

@@ -152,6 +152,44 @@ __device__ __forceinline__ int x8_pos(int64_t i) {
   return ((r >> 3) & 3) * 16 + (r >> 5) * 8 + (r & 7);
 }
 
+// X1 (data/device_dgp.py DevicePanel.bits1): the same 128 columns as bits, 1 KB per 64-row
+// block, made from X8 once per panel. One MFMA lane l (column block column c15 = l & 15, row
+// group r = l >> 4) needs rows 8r..8r+7 and 32+8r..32+8r+7 of a column per stage: 16 bits,
+// stored as one halfword. Its low byte holds the even rows and its high byte the odd rows,
+// bit t = 4 (row >> 5) + ((row >> 1) & 3), so that dword t of the lane's two fragments (rows
+// 2j, 2j+1 of half t >> 2, j = t & 3) is one shift and one AND of the halfword replicated as
+// bytes [lo, hi, hi, lo] (csrc/gram.hip bits_to_bf16x8). The halfwords of a lane's four
+// column blocks of one 64-column plane are contiguous and the planes lane-linear,
+//   byte = (col >> 6) * 512 + l * 8 + ((col >> 4) & 3) * 2 + (row & 1),
+// so a wave reads a plane with one ds_read_b64, 8 bytes per lane at stride 8: all 64 banks
+// once per 32-lane group.
+__device__ __forceinline__ int x1_byte(int cb, int row) {
+  const int l = ((row >> 3) & 3) * 16 + (cb & 15);
+  return (cb >> 6) * 512 + l * 8 + ((cb >> 4) & 3) * 2 + (row & 1);
+}
+__device__ __forceinline__ int x1_bit(int row) { return (row >> 5) * 4 + ((row >> 1) & 3); }
+
+// one thread per (row block, column, row group): 16 bytes of X8 -> one halfword of X1
+__global__ void dgp_pack_bits_kernel(const uint8_t* __restrict__ X8, int64_t nblk,
+                                     uint8_t* __restrict__ X1) {
+  const int64_t total = nblk * 512;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total;
+       e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t blk = e >> 9;
+    const int cb = (int)(e & 511) >> 2, r = (int)(e & 3);
+    const uint4 v = *reinterpret_cast<const uint4*>(X8 + blk * (128 * 64) + cb * 64 + r * 16);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t h = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int row = (k >> 3) * 32 + r * 8 + (k & 7);       // x8_pos(row) == r * 16 + k
+      const uint32_t b = (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
+      h |= (b != 0 ? 1u : 0u) << ((row & 1) * 8 + x1_bit(row));
+    }
+    *reinterpret_cast<uint16_t*>(X1 + blk * 1024 + x1_byte(cb, r * 8)) = (uint16_t)h;
+  }
+}
+
 template <typename T>
 __global__ void dgp_fill_kernel(T* __restrict__ X, int64_t cs, int64_t bs, int64_t row0, int64_t count,
                                 int64_t gid0, const int64_t* __restrict__ gids, uint64_t seed,
@@ -338,6 +376,15 @@ ATE_API int ate_dgp_fill(int dtype, void* X, int64_t cs, int64_t bs, int64_t row
                        gid0, gl, seed, p_extra, hi_lo, P, pc, (uint8_t*)X8);
   else
     return -1;
+  ATE_CHECK_LAUNCH();
+  return 0;
+}
+
+// X8: [nblk][128][64] one-byte columns (above) -> X1: [nblk][1024] bytes, their bit image
+ATE_API int ate_dgp_pack_bits(const void* X8, int64_t nblk, void* X1, void* stream) {
+  if (nblk <= 0) return 0;
+  ATE_LAUNCH(dgp_pack_bits_kernel, dim3(grid_for(nblk * 512, 256, 8192)), dim3(256), 0,
+                     (hipStream_t)stream, (const uint8_t*)X8, nblk, (uint8_t*)X1);
   ATE_CHECK_LAUNCH();
   return 0;
 }

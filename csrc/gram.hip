@@ -252,9 +252,19 @@ template <int MODE> struct PairRole {
 
 // The MFMAs of one 32-deep k-step of a wave role: a rectangle (8 A x 4 B fragments) or a
 // triangle (8 fragments as A and B, blocks m <= n in tri_index order).
-template <int MODE>
+// COLS (triangle): the same blocks column by column (n outer), so block column n needs
+// fragments 0..n only and a fragment made in registers can follow the MFMAs of the columns
+// before it; every accumulator still gets one product per call.
+template <int MODE, bool COLS = false>
 __device__ __forceinline__ void pair_mfma(f32x4* acc, const bf16x8* af, const bf16x8* bfr) {
-  if constexpr (MODE != PAIR_TRI) {
+  if constexpr (MODE == PAIR_TRI && COLS) {
+#pragma unroll
+    for (int n = 0; n < 8; ++n)
+#pragma unroll
+      for (int m = 0; m <= n; ++m)
+        acc[tri_index(m, n)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            af[m], af[n], acc[tri_index(m, n)], 0, 0, 0);
+  } else if constexpr (MODE != PAIR_TRI) {
 #pragma unroll
     for (int m = 0; m < 8; ++m)
 #pragma unroll
@@ -295,6 +305,38 @@ __device__ __forceinline__ bf16x8 bytes_to_bf16x8(uint2 d) {
 }
 constexpr int PAIR_BYTE0 = 384;   // first one-byte column (P == 512)
 
+// Bit columns (COL_BITS; the same 128 columns from the panel's bit image, csrc/dgp.hip
+// x1_byte): 16 bytes per row and 1 KB per stage instead of 128 and 8 KB, so a chunk streams
+// 784 bytes per row. The 1 KB is one LDS-DMA piece (wave 0 copies it verbatim). A lane's 16
+// bits of a column -- both halves' rows -- are one halfword: low byte the even rows, high
+// byte the odd rows, bit t for rows 2j, 2j+1 of half t >> 2 (j = t & 3). The halfwords of
+// the four column blocks of a 64-column plane are 8 contiguous bytes per lane, lane-linear:
+// a rectangle wave reads its plane with one ds_read_b64 per stage and a triangle wave both
+// planes with two (stride 8 over 32 lanes: every bank once per lane group). bits_rep spreads
+// a halfword as bytes [lo, hi, hi, lo]; dword t of the fragments is then (w << (14 - t)) &
+// 0x40004000: a one is bf16 0x4000 = 2.0, so the products are exact doubles (or fourfolds)
+// and the slab reduce scales them back by 0.5 per bit column: the same Gram bits.
+template <int HW>
+__device__ __forceinline__ uint32_t bits_rep(uint32_t d) {
+  return __builtin_amdgcn_perm(0u, d, HW ? 0x02030302u : 0x00010100u);
+}
+template <int H>
+__device__ __forceinline__ bf16x8 bits_to_bf16x8(uint32_t w) {
+  uint4 v;
+  v.x = (w << (14 - 4 * H)) & 0x40004000u;
+  v.y = (w << (13 - 4 * H)) & 0x40004000u;
+  v.z = (w << (12 - 4 * H)) & 0x40004000u;
+  v.w = (w << (11 - 4 * H)) & 0x40004000u;
+  return __builtin_bit_cast(bf16x8, v);
+}
+// column modes of the paired-tile kernel: all bf16, or physical columns 384..511 as one-byte
+// or as bit columns
+constexpr int COL_BF16 = 0, COL_BYTES = 1, COL_BITS = 2;
+template <int MASK, int N>
+__device__ __forceinline__ void sched_group() {
+  if constexpr (N > 0) __builtin_amdgcn_sched_group_barrier(MASK, N, 0);
+}
+
 // Schedules of the double-buffered K-loop (ate_gram_bf16_pair `sched`, ops/gram.py GRAM_SCHED):
 // lockstep: all eight waves run one program; stagger: waves 4-7 run half a stage behind their
 // SIMD partners 0-3 (LATE below). An L2 warm-ahead of the panel stream was measured with both
@@ -312,12 +354,15 @@ constexpr int SCHED_LOCKSTEP = 0, SCHED_STAGGER = 1;
 // reads stage s from LDS only between barriers s-1 and s and executes 1 + nsteps barriers
 // (the loop's barriers sit outside every role- or idle-dependent branch), and every
 // accumulator still adds half 0 then half 1 of the stages in stage order: the same bits.
-template <int MODE, bool BYTES, bool BY, bool LATE, bool SADDR>
+// CM: the launch's column mode (COL_*; X8 = the byte or the bit image, null for COL_BF16).
+template <int MODE, int CM, bool BY, bool LATE, bool SADDR>
 __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t cs, int64_t bs, int a0,
                                           int b0, bool haveB, bool idle, int abuf, int bbuf,
                                           int arow0, int bcol0, const Chunk& ch,
                                           bf16_t* lds_raw, float* __restrict__ out,
                                           const uint8_t* __restrict__ X8) {
+  constexpr bool BYTES = CM != COL_BF16;   // tile b's columns 128..255 are not staged as bf16
+  constexpr bool BITS = CM == COL_BITS;
   constexpr bool TRI = PairRole<MODE>::TRI;
   constexpr int NB = PairRole<MODE>::NB;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -331,7 +376,8 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
   // instead of a pointer per piece (the late waves have none to spare)
   const int wu = __builtin_amdgcn_readfirstlane(wid);
   const uint32_t voff_ = (uint32_t)(((lane >> 3) * cs + (((lane & 7) ^ (lane >> 3)) << 3)) * 2);
-  const uint32_t voff8_ = (uint32_t)((lane >> 2) * GK + (((lane & 3) ^ ((lane >> 3) & 2)) << 4));
+  const uint32_t voff8_ = BITS ? (uint32_t)(lane * 16)
+                               : (uint32_t)((lane >> 2) * GK + (((lane & 3) ^ ((lane >> 3) & 2)) << 4));
   auto stage = [&](int st, int64_t i0) {
     if constexpr (SADDR) {
       gptr_t Xk0 = (gptr_t) reinterpret_cast<const char*>(X + (i0 >> 6) * bs);
@@ -355,10 +401,36 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
           const int q = wu * 2 + r;
           glds16(Xk0 + (int64_t)(b0 + q * 8) * cs * 2 + voff, &lds[st][1][q * 8 * GK]);
         }
-        glds16((gptr_t) reinterpret_cast<const char*>(X8) + (i0 >> 6) * (128 * GK) + wu * 1024 + voff8,
-               reinterpret_cast<bf16_t*>(reinterpret_cast<uint8_t*>(&lds[st][1][128 * GK]) +
-                                         wu * 1024));
+        if constexpr (BITS) {
+          // the stage's 1 KB of bits, verbatim (voff8 = 16 * lane): one piece, wave 0
+          if (wu == 0)
+            glds16((gptr_t) reinterpret_cast<const char*>(X8) + (i0 >> 6) * 1024 + voff8,
+                   &lds[st][1][128 * GK]);
+        } else {
+          glds16((gptr_t) reinterpret_cast<const char*>(X8) + (i0 >> 6) * (128 * GK) + wu * 1024 + voff8,
+                 reinterpret_cast<bf16_t*>(reinterpret_cast<uint8_t*>(&lds[st][1][128 * GK]) +
+                                           wu * 1024));
+        }
       }
+      return;
+    }
+    if constexpr (BITS) {
+      const bf16_t* Xk0 = X + (i0 >> 6) * bs;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int q = wid * 4 + r;
+        const int col = q * 8 + (lane >> 3);
+        const int cc = (lane & 7) ^ (col & 7);
+        glds16(Xk0 + cc * 8 + (int64_t)(a0 + col) * cs, &lds[st][0][q * 8 * GK]);
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int q = wid * 2 + r;
+        const int col = q * 8 + (lane >> 3);
+        const int cc = (lane & 7) ^ (col & 7);
+        glds16(Xk0 + cc * 8 + (int64_t)(b0 + col) * cs, &lds[st][1][q * 8 * GK]);
+      }
+      if (wu == 0) glds16(X8 + (i0 >> 6) * 1024 + lane * 16, &lds[st][1][128 * GK]);
       return;
     }
     if constexpr (BYTES) {
@@ -410,6 +482,16 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
     const int slot = (lane >> 4) ^ ((cb >> 1) & 2);
     return *reinterpret_cast<const uint4*>(b8 + cb * GK + slot * 16);
   };
+  // bit columns: the lane's replicated halfwords of the four column blocks from image column
+  // col0 (128 or 192: plane 0 or 1), one ds_read_b64
+  auto bits4 = [&](const bf16_t* P_, int col0, uint32_t* w) {
+    const uint8_t* b1 = reinterpret_cast<const uint8_t*>(P_ + 128 * GK);
+    const uint2 q = *reinterpret_cast<const uint2*>(b1 + ((col0 - 128) >> 6) * 512 + lane * 8);
+    w[0] = bits_rep<0>(q.x);
+    w[1] = bits_rep<1>(q.x);
+    w[2] = bits_rep<0>(q.y);
+    w[3] = bits_rep<1>(q.y);
+  };
   const int64_t nsteps = (ch.row1 - ch.row0) / GK;
   if (nsteps > 0) stage(0, ch.row0);
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
@@ -431,10 +513,46 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
     if constexpr (LATE) {
       // half 1 of stage s-1 from registers beside the reads of half 0 of stage s ...
       bf16x8 na[8], nb[TRI ? 1 : 4];
-      uint4 raw[BY ? (TRI ? 8 : 4) : 1];
+      uint4 raw[BY && !BITS ? (TRI ? 8 : 4) : 1];
+      uint32_t bw[BY && BITS ? (TRI ? 8 : 4) : 1];
       const int c0 = lane >> 4, c1 = 4 + (lane >> 4);
       if (!idle) {
-        if constexpr (BY && !TRI) {
+        if constexpr (BY && BITS && !TRI) {
+          bits4(Bs, bcol0, bw);
+#pragma unroll
+          for (int m = 0; m < 8; ++m) na[m] = frag(As, arow0 + m * 16 + (lane & 15), c0);
+          // (the B halfwords stay packed until the second block)
+          pair_mfma<MODE>(acc, ha, hb);
+#pragma unroll
+          for (int i = 0; i < 9; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);      // bits_rep
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 10, 0);
+        } else if constexpr (BY && BITS) {
+          bits4(As, arow0, bw);
+          bits4(As, arow0 + 64, bw + 4);
+#pragma unroll
+          for (int m = 0; m < 8; ++m) na[m] = bits_to_bf16x8<0>(bw[m]);
+          pair_mfma<MODE>(acc, ha, ha);
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 32; ++i) {                          // bits_rep, then half 0
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+          }
+        } else if constexpr (BY && !TRI) {
 #pragma unroll
           for (int n = 0; n < 4; ++n) raw[n] = raw16(Bs, bcol0 + n * 16 + (lane & 15));
 #pragma unroll
@@ -492,7 +610,42 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
       if (s + 1 < nsteps) stage(cur ^ 1, ch.row0 + (s + 1) * GK);
       // ... and half 0 of stage s beside the reads of its half 1 into the registers just freed
       if (!idle) {
-        if constexpr (BY && !TRI) {
+        if constexpr (BY && BITS && !TRI) {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) ha[m] = frag(As, arow0 + m * 16 + (lane & 15), c1);
+#pragma unroll
+          for (int n = 0; n < 4; ++n) nb[n] = bits_to_bf16x8<0>(bw[n]);
+#pragma unroll
+          for (int n = 0; n < 4; ++n) hb[n] = bits_to_bf16x8<1>(bw[n]);
+          pair_mfma<MODE>(acc, na, nb);
+          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);      // B fragment 0 of half 0
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {                           // fragments 1-3 beside the
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // first MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 27, 0);
+        } else if constexpr (BY && BITS) {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) ha[m] = bits_to_bf16x8<1>(bw[m]);
+          pair_mfma<MODE>(acc, na, na);
+#pragma unroll
+          for (int i = 0; i < 32; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NB - 32, 0);
+        } else if constexpr (BY && !TRI) {
 #pragma unroll
           for (int m = 0; m < 8; ++m) ha[m] = frag(As, arow0 + m * 16 + (lane & 15), c1);
 #pragma unroll
@@ -556,7 +709,60 @@ __device__ __forceinline__ void pair_wave(const bf16_t* __restrict__ X, int64_t 
       // every fragment of the stage (both 32-row halves) read from LDS up front, then the
       // MFMAs: the waits on LDS leave the MFMA chains of the stage
       if (!idle) {
-        if constexpr (BY && !TRI) {
+        if constexpr (BY && BITS && !TRI) {
+          // bit B fragments: one 8-byte read holds both halves' rows of the wave's 64 columns;
+          // half 0 widened ahead of its MFMAs (while the A reads are in flight), half 1 beside
+          // half 0's MFMAs
+          bf16x8 af[2][8];
+          uint32_t w4[4];
+          bits4(Bs, bcol0, w4);
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            const int cc = kk * 4 + (lane >> 4);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) af[kk][m] = frag(As, arow0 + m * 16 + (lane & 15), cc);
+          }
+          bf16x8 b0v[4], b1v[4];
+#pragma unroll
+          for (int n = 0; n < 4; ++n) b0v[n] = bits_to_bf16x8<0>(w4[n]);
+#pragma unroll
+          for (int n = 0; n < 4; ++n) b1v[n] = bits_to_bf16x8<1>(w4[n]);
+          pair_mfma<MODE>(acc, af[0], b0v);
+          pair_mfma<MODE>(acc, af[1], b1v);
+          __builtin_amdgcn_sched_group_barrier(0x100, 9, 0);      // bits + A half 0
+          __builtin_amdgcn_sched_group_barrier(0x002, 36, 0);     // bits_rep + half 0
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {                           // A half 1 reads beside
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // half 0's MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {                          // half 1 widened beside
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // the next MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB - 24, 0);
+        } else if constexpr (BY && BITS) {
+          // bit triangle: block column n of a half needs fragments 0..n, so fragment n + 1 is
+          // widened beside column n's MFMAs and half 1's fragment 0 beside half 0's last column
+          uint32_t w8[8];
+          bits4(As, arow0, w8);
+          bits4(As, arow0 + 64, w8 + 4);
+          bf16x8 f0[8], f1[8];
+#pragma unroll
+          for (int m = 0; m < 8; ++m) f0[m] = bits_to_bf16x8<0>(w8[m]);
+#pragma unroll
+          for (int m = 0; m < 8; ++m) f1[m] = bits_to_bf16x8<1>(w8[m]);
+          pair_mfma<MODE, true>(acc, f0, f0);
+          pair_mfma<MODE, true>(acc, f1, f1);
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);     // bits_rep + fragment 0
+#define TRI_COL(C) sched_group<0x008, 1>(); sched_group<0x002, 8>(); sched_group<0x008, C>();
+          TRI_COL(0) TRI_COL(1) TRI_COL(2) TRI_COL(3) TRI_COL(4) TRI_COL(5) TRI_COL(6) TRI_COL(7)
+          TRI_COL(0) TRI_COL(1) TRI_COL(2) TRI_COL(3) TRI_COL(4) TRI_COL(5) TRI_COL(6)
+#undef TRI_COL
+          __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+        } else if constexpr (BY && !TRI) {
           // byte B fragments: one 16-byte read per column holds both halves' rows, converted
           // per half just ahead of its MFMAs; the second half's conversion interleaved with the
           // first half's MFMAs (mask 0x002 VALU)
@@ -679,9 +885,10 @@ extern "C" __attribute__((visibility("default"))) int ate_gram_clock_reset() {
 }
 #endif
 
+// CM: the column mode (COL_*; X8 = the byte copy or the bit image of columns 384..511).
 // SCHED: the K-loop schedule (SCHED_*). prio: s_setprio 1 for waves 4-7 (0 = none, 1 = every
 // workgroup, 2 = diagonal-pair workgroups only; GRAM_PRIO).
-template <bool BYTES, int SCHED>
+template <int CM, int SCHED>
 __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
     const bf16_t* __restrict__ X, int64_t cs, int64_t bs, const int4* __restrict__ tiles, int ntiles,
     const Chunk* __restrict__ chunks, int nchunks, float* __restrict__ slab,
@@ -723,12 +930,13 @@ __global__ __launch_bounds__(512) void gram_bf16_pair_kernel(
     __builtin_amdgcn_s_setprio(1);
   // byte fragments: tile b's columns 128..255 (type 0: the waves of B columns 128..255;
   // type 1, tile b: the rectangle waves' B and the second triangle)
+  constexpr bool BYTES = CM != COL_BF16;
   const bool by = BYTES && (type == 0 ? (wid & 3) >= 2 : region == 1 && (!tri || half == 1));
   ATE_DASSERT(!BYTES || (X8 != nullptr && ntiles == 2 && b0 == 256));
   // waves 4-7 (the triangle waves of a diagonal pair, half of the rectangle waves of an
   // off-diagonal tile) are the late ones of the stagger schedule
   constexpr bool STAG = (SCHED & SCHED_STAGGER) != 0;
-#define PAIR_WAVE(M, B, L) pair_wave<M, BYTES, B, L, SCHED != SCHED_LOCKSTEP>(                      \
+#define PAIR_WAVE(M, B, L) pair_wave<M, CM, B, L, SCHED != SCHED_LOCKSTEP>(                         \
       X, cs, bs, a0, b0, haveB, idle, abuf, bbuf, arow0, bcol0, ch, lds, out, X8)
 #define PAIR_WAVE_BY(M, L) do { if (by) PAIR_WAVE(M, BYTES, L); else PAIR_WAVE(M, false, L); } while (0)
   if (tri) PAIR_WAVE_BY(PAIR_TRI, STAG);
@@ -764,12 +972,13 @@ __device__ __forceinline__ void gram_limbs(double v, long long& hi, long long& l
 // blocks: [ntiles][PAIR_SLOTS] int2 (I, J) = 16-column block coordinates of the Gram (I: A
 // side = row), (-1, -1) = unused slot. Blocks with I == J are full 16x16 diagonal blocks: only
 // their r <= c entries are written (plus mirror), so every Gram entry has ONE writer.
-// byte0: first one-byte column (their slab partials are halves: scaled back by 2 per byte
-// column, exactly), P when there are none.
+// byte0: first one-byte or bit column, P when there are none. Their slab partials are exact
+// power-of-two multiples (a one was 0.5 as a byte, 2.0 as a bit): scaled back by bsc = 2 or
+// 0.5 per such column, exactly.
 __global__ void gram_pair_reduce_kernel(const float* __restrict__ slab, const int2* __restrict__ blocks,
                                         int ntiles, int slots, const int* __restrict__ seg_chunk0,
                                         int nseg, int P, double* __restrict__ G,
-                                        long long* __restrict__ Gx, int byte0) {
+                                        long long* __restrict__ Gx, int byte0, double bsc) {
   const int64_t per = (int64_t)ntiles * slots * 256;
   const int64_t total = (int64_t)nseg * per;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total;
@@ -787,7 +996,7 @@ __global__ void gram_pair_reduce_kernel(const float* __restrict__ slab, const in
     const float* src = slab + rem;
     const int a = bl.x * 16 + r, b = bl.y * 16 + cl;
     ATE_DASSERT(s < nseg && c0 >= 0 && c0 <= c1 && a >= 0 && a < P && b >= 0 && b < P);
-    const double sc = (a >= byte0 ? 2.0 : 1.0) * (b >= byte0 ? 2.0 : 1.0);
+    const double sc = (a >= byte0 ? bsc : 1.0) * (b >= byte0 ? bsc : 1.0);
     if (Gx) {                                       // exact mode: int64 limbs
       long long hs = 0, ls = 0;
       int ci = c0;
@@ -838,22 +1047,24 @@ __global__ void gram_pair_reduce_kernel(const float* __restrict__ slab, const in
 #define PAIR_SCHEDS(F) F(0) F(1)
 #define PAIR_SHAPE(S)                                                                     \
   static ate::KernelShapeReg ate_kshape_pair_##S(                                         \
-      (const void*)(gram_bf16_pair_kernel<false, S>), "gram_bf16_pair_kernel<sched " #S ">", 512, 0); \
+      (const void*)(gram_bf16_pair_kernel<COL_BF16, S>), "gram_bf16_pair_kernel<sched " #S ">", 512, 0); \
   static ate::KernelShapeReg ate_kshape_pair8_##S(                                        \
-      (const void*)(gram_bf16_pair_kernel<true, S>), "gram_bf16_pair_kernel<bytes, sched " #S ">", 512, 0);
+      (const void*)(gram_bf16_pair_kernel<COL_BYTES, S>), "gram_bf16_pair_kernel<bytes, sched " #S ">", 512, 0); \
+  static ate::KernelShapeReg ate_kshape_pair1_##S(                                        \
+      (const void*)(gram_bf16_pair_kernel<COL_BITS, S>), "gram_bf16_pair_kernel<bits, sched " #S ">", 512, 0);
 PAIR_SCHEDS(PAIR_SHAPE)
 #undef PAIR_SHAPE
 ATE_KERNEL_SHAPE("gram_bf16_256_kernel", 512, 0, gram_bf16_256_kernel)
 ATE_KERNEL_SHAPE("gram_bf16_kernel", 256, 0, gram_bf16_kernel)
 
-// what: 1 = tile kernel (slab partials), 2 = fixed-order slab reduce into G, 3 = both.
-// Split so a caller can run the reduce on another stream than the next tile kernel.
-// X8: the one-byte copies of columns 384..511 (P == 512 only), or null.
-ATE_API int ate_gram_bf16_pair(const void* X, int64_t cs, int64_t bs, int P, const void* tiles, int ntiles,
-                               const void* blocks, const void* chunks, int nchunks,
-                               const void* seg_chunk0, int nseg, void* slab, void* G, int what,
-                               void* Gx, const void* X8, int sched, int prio, void* stream) {
+// cm: COL_*; X8: the one-byte copies (COL_BYTES) or the bit image (COL_BITS) of columns
+// 384..511, null for COL_BF16
+static int gram_pair(int cm, const void* X, int64_t cs, int64_t bs, int P, const void* tiles,
+                     int ntiles, const void* blocks, const void* chunks, int nchunks,
+                     const void* seg_chunk0, int nseg, void* slab, void* G, int what, void* Gx,
+                     const void* X8, int sched, int prio, void* stream) {
   if (P % (2 * GT) || what < 1 || what > 3) return -1;
+  if ((cm != COL_BF16) != (X8 != nullptr)) return -1;
   if (X8 != nullptr && (P != 512 || ntiles != 2)) return -1;
   // the other schedules address a piece's 8 columns with a 32-bit per-lane byte offset
   if (sched != SCHED_LOCKSTEP && cs >= ((int64_t)1 << 28)) return -1;
@@ -863,20 +1074,20 @@ ATE_API int ate_gram_bf16_pair(const void* X, int64_t cs, int64_t bs, int P, con
   if (prio > 2) return -1;
   hipStream_t s = (hipStream_t)stream;
   if (what & 1) {
+#define PAIR_LAUNCH_CM(C, S)                                                                  \
+  ATE_LAUNCH((gram_bf16_pair_kernel<C, S>), dim3(nchunks * ntiles), dim3(512), 0, s,          \
+             (const bf16_t*)X, cs, bs, (const int4*)tiles, ntiles, (const Chunk*)chunks,      \
+             nchunks, (float*)slab, (const uint8_t*)X8, prio)
     switch (sched) {
 #define PAIR_LAUNCH(S)                                                                        \
   case S:                                                                                     \
-    if (X8 != nullptr)                                                                        \
-      ATE_LAUNCH((gram_bf16_pair_kernel<true, S>), dim3(nchunks * ntiles), dim3(512), 0, s,   \
-                 (const bf16_t*)X, cs, bs, (const int4*)tiles, ntiles, (const Chunk*)chunks,  \
-                 nchunks, (float*)slab, (const uint8_t*)X8, prio);                            \
-    else                                                                                      \
-      ATE_LAUNCH((gram_bf16_pair_kernel<false, S>), dim3(nchunks * ntiles), dim3(512), 0, s,  \
-                 (const bf16_t*)X, cs, bs, (const int4*)tiles, ntiles, (const Chunk*)chunks,  \
-                 nchunks, (float*)slab, (const uint8_t*)nullptr, prio);                       \
+    if (cm == COL_BITS) PAIR_LAUNCH_CM(COL_BITS, S);                                          \
+    else if (cm == COL_BYTES) PAIR_LAUNCH_CM(COL_BYTES, S);                                   \
+    else PAIR_LAUNCH_CM(COL_BF16, S);                                                         \
     break;
       PAIR_SCHEDS(PAIR_LAUNCH)
 #undef PAIR_LAUNCH
+#undef PAIR_LAUNCH_CM
       default: return -1;   // a schedule this library was not built with
     }
     ATE_CHECK_LAUNCH();
@@ -886,10 +1097,32 @@ ATE_API int ate_gram_bf16_pair(const void* X, int64_t cs, int64_t bs, int P, con
     ATE_LAUNCH(gram_pair_reduce_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, s,
                        (const float*)slab, (const int2*)blocks, ntiles, PAIR_SLOTS,
                        (const int*)seg_chunk0, nseg, P, (double*)G, (long long*)Gx,
-                       X8 != nullptr ? PAIR_BYTE0 : P);
+                       X8 != nullptr ? PAIR_BYTE0 : P, cm == COL_BITS ? 0.5 : 2.0);
     ATE_CHECK_LAUNCH();
   }
   return 0;
+}
+
+// what: 1 = tile kernel (slab partials), 2 = fixed-order slab reduce into G, 3 = both.
+// Split so a caller can run the reduce on another stream than the next tile kernel.
+// X8: the one-byte copies of columns 384..511 (P == 512 only), or null.
+ATE_API int ate_gram_bf16_pair(const void* X, int64_t cs, int64_t bs, int P, const void* tiles, int ntiles,
+                               const void* blocks, const void* chunks, int nchunks,
+                               const void* seg_chunk0, int nseg, void* slab, void* G, int what,
+                               void* Gx, const void* X8, int sched, int prio, void* stream) {
+  return gram_pair(X8 != nullptr ? COL_BYTES : COL_BF16, X, cs, bs, P, tiles, ntiles, blocks,
+                   chunks, nchunks, seg_chunk0, nseg, slab, G, what, Gx, X8, sched, prio, stream);
+}
+
+// The same with columns 384..511 streamed from the panel's bit image X1 ([ld / 64][1024]
+// bytes, csrc/dgp.hip ate_dgp_pack_bits): P == 512 only, X1 not null.
+ATE_API int ate_gram_bf16_pair_bits(const void* X, int64_t cs, int64_t bs, int P, const void* tiles,
+                                    int ntiles, const void* blocks, const void* chunks, int nchunks,
+                                    const void* seg_chunk0, int nseg, void* slab, void* G, int what,
+                                    void* Gx, const void* X1, int sched, int prio, void* stream) {
+  if (X1 == nullptr) return -1;
+  return gram_pair(COL_BITS, X, cs, bs, P, tiles, ntiles, blocks, chunks, nchunks, seg_chunk0,
+                   nseg, slab, G, what, Gx, X1, sched, prio, stream);
 }
 
 // ------------------------------------------------------------------ fp32 / fp64 64x64

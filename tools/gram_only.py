@@ -1,6 +1,7 @@
 """Run the bf16 Gram kernel alone on the N=1e7, p=500 bench panel (A/B of the 256-tile
-kernel variants, and for PMC profiling). Usage: gram_only.py [N] [pair|pair16|tile256 ...];
-pair and pair16 take a K-loop schedule suffix (pair:lockstep, pair:stagger: ops/gram.py
+kernel variants, and for PMC profiling). Usage: gram_only.py [N] [pair|pair8|pair16|tile256 ...]
+(pair: the panel's {0, 1} columns streamed as bits, pair8: as bytes, pair16: as bf16);
+the pair variants take a K-loop schedule suffix (pair:lockstep, pair:stagger: ops/gram.py
 SCHEDULES); ATE_BLOCKED=0 for a column-major panel"""
 import os
 import sys
@@ -20,13 +21,15 @@ pan = synthetic_panel(n, p=500, folds=5, seed=1991, dtype="bf16", device=torch.d
                       blocked=os.environ.get("ATE_BLOCKED", "1") == "1",
                       dgp=os.environ.get("ATE_DGP", "tutorial"))
 ref = None
-stage = os.environ.get("ATE_GRAM_STAGE", "all")   # "tiles": the tile kernel alone (no slab reduce)
+bits1 = pan.bits1
+stage =os.environ.get("ATE_GRAM_STAGE", "all")   # "tiles": the tile kernel alone (no slab reduce)
 sched0 = gram_mod.GRAM_SCHED
 for name in variants:
     v, _, sched = name.partition(":")
     gram_mod.GRAM_SCHED = sched or sched0
-    gram_mod.GRAM_KERNEL = "pair" if v == "pair16" else v
+    gram_mod.GRAM_KERNEL = "pair" if v in ("pair16", "pair8") else v
     gram_mod.BYTE_COLS = v != "pair16"      # pair16: the panel's byte columns read as bf16
+    pan.bits1 = None if v == "pair8" else bits1   # pair8: the byte copy, not the bit image
     gram_mod._plan_cache.clear()
     for _ in range(3):
         G = gram_mod.gram(pan)
