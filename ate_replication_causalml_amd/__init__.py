@@ -38,11 +38,11 @@ if _want > 0 and int(_old or 0) < _want:
                        "any GPU call)", RuntimeWarning, stacklevel=2)
 from .api import (Replication, ate_aipw_crossfit, ate_aipw_glm, ate_aipw_rf, ate_belloni, ate_causal_forest,
                   ate_causal_forest_bootstrap,
-                  ate_dml, ate_dml_apos, ate_dml_iivm, ate_dml_irm, ate_dml_irm_cate, ate_dml_irm_gate, ate_dml_irm_policy, ate_dml_irm_sensitivity, ate_dml_irm_targets, ate_dml_pliv, ate_double_ml, ate_ipw, ate_ipw_wls, ate_lasso, ate_lasso_single,
+                  ate_dml, ate_dml_apos, ate_dml_iivm, ate_dml_irm, ate_dml_irm_cate, ate_dml_irm_gate, ate_dml_irm_policy, ate_dml_irm_rate, ate_dml_irm_sensitivity, ate_dml_irm_targets, ate_dml_pliv, ate_double_ml, ate_ipw, ate_ipw_wls, ate_lasso, ate_lasso_single,
                   ate_naive, ate_ols, ate_residual_balance, propensity_lasso,
                   propensity_logistic, replicate)
 from .config import BalanceConfig, CvConfig, ForestConfig, ReplicateConfig, RunConfig
-from .result import (ApoResult, AteResult, CateResult, GateResult, LateResult, PlivResult, PolicyTreeResult, SensitivityResult, TargetResult,
+from .result import (ApoResult, AteResult, CateResult, GateResult, LateResult, PlivResult, PolicyTreeResult, RateResult, SensitivityResult, TargetResult,
                      format_table, results_frame)
 
 __version__ = "0.1.0"

@@ -122,6 +122,8 @@ _SIGS = {
     "ate_cate_moments_scratch": "iii",
     "ate_cate_boot": "ppplppiiiuippp",
     "ate_cate_boot_scratch": "iiii",
+    "ate_rate_boot": "pppplliiuippp",
+    "ate_rate_boot_scratch": "iii",
     "ate_policy_pair_hist": "ppppppliiipp",
     "ate_policy_pair_hist_scratch": "i",
     "ate_policy_search": "ppiilppp",
@@ -173,6 +175,7 @@ _RESTYPE = {"ate_forest_scratch_bytes": ctypes.c_int64,
             "ate_scan_parts": ctypes.c_int64, "ate_group_boot_scratch": ctypes.c_int64,
             "ate_cate_moments_scratch": ctypes.c_int64,
             "ate_cate_boot_scratch": ctypes.c_int64,
+            "ate_rate_boot_scratch": ctypes.c_int64,
             "ate_policy_pair_hist_scratch": ctypes.c_int64,
             "ate_cluster_work": ctypes.c_int64}
 _CT = {"p": c_void_p, "i": c_int, "l": c_int64, "u": c_uint64, "d": c_double}

@@ -23,6 +23,8 @@ its effect curve along one covariate on a B-spline basis with a uniform band (Do
 cate(basis) / confint(joint=True)) -> ate_dml_irm_cate;
 the exact depth-2 policy tree on its scores (DoubleML policy_tree, searched exactly as
 policytree does) -> ate_dml_irm_policy;
+the evaluation of a treatment-priority rule on its scores: AUTOC, Qini and the TOC curve with
+half-sample bootstrap SEs (grf rank_average_treatment_effect) -> ate_dml_irm_rate;
 its sensitivity to unobserved confounding (DoubleML sensitivity_analysis /
 sensitivity_benchmark) -> ate_dml_irm_sensitivity;
 its effect on the treated and on the controls with the joint covariance (DoubleML
@@ -42,7 +44,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .config import METHODS, BalanceConfig, ReplicateConfig, RunConfig
-from .result import (ApoResult, AteResult, CateResult, GateResult, LateResult, PlivResult, PolicyTreeResult, SensitivityResult,
+from .result import (ApoResult, AteResult, CateResult, GateResult, LateResult, PlivResult, PolicyTreeResult, RateResult,
+                     SensitivityResult,
                      TargetResult, format_table, results_frame)
 from .utils import guards
 from .utils.tracing import trace
@@ -392,6 +395,44 @@ def ate_dml_irm_policy(Y, W, X, features, depth=2, bins=32, min_leaf=1, cost=0.0
         from .estimators import policy as DP
         return DP.dml_irm_policy_lasso(Y, W, X, features, device=run.device(), dtype=run.dtype,
                                        **kw)
+
+
+def ate_dml_irm_rate(Y, W, X, priority, q=None, subset=None, n_boot=200, level=0.95, folds=5,
+                     lambda_rule="min", clip=0.01, run=None, propensity="linear",
+                     clusters=None, repeats=1) -> RateResult:
+    """Does treating in the order of ``priority`` (an (n,) vector, or a column index into X;
+    higher = first, ties enter together) find the rows with large effects: the TOC curve on
+    the grid ``q`` (default 0.1, ..., 1.0; at most 64 strictly increasing points in (0, 1]),
+    its area AUTOC and the Qini coefficient of the AIPW scores of ate_dml_irm, with
+    half-sample bootstrap standard errors from ``n_boot`` replicates, normal ``level``
+    intervals, two-sided p-values and a uniform band over the curve (estimators/rate.py;
+    grf's rank_average_treatment_effect). AUTOC / SE is the test for heterogeneity that the
+    rule can exploit. ``subset``: a boolean mask of the evaluation rows (default: all).
+
+    A priority fitted on the evaluation rows' own outcomes -- the tree of ate_dml_irm_policy
+    or the curve of ate_dml_irm_cate from the same rows -- gives an optimistic RATE. Fit the
+    rule on other rows and evaluate on the rest: ``ate_dml_irm_policy(train=mask)``, then
+    ``subset=~mask`` here.
+
+    ValueError: ``clusters``, ``repeats`` != 1, row shards, a non-finite priority on an
+    evaluation row, fewer than 128 evaluation rows, a first grid point entering fewer than
+    64 rows, 2^27 or more evaluation rows."""
+    run = _run(run)
+    with trace("ate_dml_irm_rate", folds=folds, n_boot=n_boot):
+        from .estimators import rate as DR
+        if clusters is not None:
+            raise ValueError("ate_dml_irm_rate does not support clusters")
+        if repeats != 1:
+            raise ValueError("ate_dml_irm_rate does not support repeated cross-fitting")
+        if _ref(run):
+            from .reference import estimators as R
+            return R.dml_irm_rate(Y, W, X, priority, q=q, subset=subset, n_boot=n_boot,
+                                  level=level, folds=folds, seed=run.seed,
+                                  lambda_rule=lambda_rule, clip=clip, propensity=propensity)
+        return DR.dml_irm_rate_lasso(Y, W, X, priority, q=q, subset=subset, n_boot=n_boot,
+                                     level=level, folds=folds, seed=run.seed,
+                                     lambda_rule=lambda_rule, clip=clip, device=run.device(),
+                                     dtype=run.dtype, propensity=propensity)
 
 
 def ate_dml_irm_sensitivity(Y, W, X, cf_y=0.03, cf_d=0.03, rho=1.0, level=0.95, null=0.0,

@@ -55,6 +55,11 @@ def _dml(a):
             raise SystemExit(str(e))
         if pk and a.sensitivity:
             raise SystemExit("--propensity logit is not available with --sensitivity")
+        if a.rate_col is not None and (
+                a.repeats > 1 or a.gate_col is not None or a.cate_col is not None
+                or a.policy_cols is not None or a.sensitivity or a.targets is not None):
+            raise SystemExit("--rate-col is an analysis of its own: not with --repeats, "
+                             "--gate-col, --cate-col, --policy-cols, --sensitivity or --targets")
         if a.repeats > 1:
             # repeated cross-fitting: 2 K*K micro-arm segments, `repeats` K-fold partitions
             if (a.gate_col is not None or a.cate_col is not None or a.policy_cols is not None
@@ -100,6 +105,34 @@ def _dml(a):
                 from dataclasses import asdict
                 out["contrast"] = asdict(r.contrast("treated", "control"))
             print(json.dumps(out))
+            return 0
+        if a.rate_col is not None:
+            # does treating by covariate x{rate_col}, largest first, find the large effects:
+            # AUTOC, QINI and the TOC curve with half-sample bootstrap SEs
+            import numpy as np
+            from .estimators import rate as DR
+            from .estimators.irm import run_phases
+            from .result import RateResult
+            if not 0 <= a.rate_col < a.p:
+                raise SystemExit(f"--rate-col must index the {a.p} covariates")
+            if not 1 <= a.rate_grid <= DR.GRID_MAX:
+                raise SystemExit(f"--rate-grid must be in [1, {DR.GRID_MAX}]")
+            grid = np.arange(1, a.rate_grid + 1) / a.rate_grid
+            rid = pan.row_index
+            try:
+                DR.check_boot(a.boot)
+                order, flags = DR.rate_order(pan.col(f"x{a.rate_col}").double(), rid, None, grid)
+                if order.numel() < DR.ROWS_MIN or int(DR.rate_entered(flags)[0]) < DR.FIRST_MIN:
+                    raise ValueError(f"RATE needs at least {DR.ROWS_MIN} rows and a first grid "
+                                     f"point entering at least {DR.FIRST_MIN}")
+                st = run_phases(DR.rate_phases(pan, rid, order, flags, a.rate_grid, a.folds,
+                                               a.lambda_rule, a.clip, a.boot, 0.95, a.seed, **pk))
+            except ValueError as e:
+                raise SystemExit(str(e))
+            r = RateResult.make("DML-IRM RATE (LASSO)", grid, DR.rate_entered(flags).cpu().numpy(),
+                                st["fin"].double().cpu().numpy(), order.numel(),
+                                int((flags & 1).sum().item()), a.boot, 0.95)
+            print(json.dumps({**json.loads(r.json()), **pk}))
             return 0
         if a.gate_col is not None and a.sensitivity:
             raise SystemExit("--gate-col and --sensitivity are separate analyses: pick one")
@@ -370,6 +403,11 @@ def main(argv=None):
     d.add_argument("--cate-degree", type=int, default=3, help="irm --cate-col: spline degree 0..3")
     d.add_argument("--cate-grid", type=int, default=100,
                    help="irm --cate-col: points of the curve, between the 5 %% and 95 %% quantiles")
+    d.add_argument("--rate-col", type=int, default=None,
+                   help="irm: AUTOC, QINI and the TOC curve of treating by covariate x{J}, largest "
+                        "first (half-sample bootstrap SEs; --boot replicates)")
+    d.add_argument("--rate-grid", type=int, default=10,
+                   help="irm --rate-col: points of the TOC curve, u = 1/Q, ..., 1")
     d.add_argument("--policy-cols", default=None, metavar="J,J,...",
                    help="irm: the exact policy tree (whom to treat) over the covariates x{J}, ...")
     d.add_argument("--policy-depth", type=int, default=2, help="irm --policy-cols: depth 0..2")

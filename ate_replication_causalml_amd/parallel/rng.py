@@ -34,6 +34,7 @@ P_SAMPLE_ROWS = 8   # sample_n row selection in the data pipeline
 P_MULT = 9          # Rademacher multipliers of the grouped multiplier bootstrap (csrc/gate.hip)
 P_BAND = 10         # normals of the simultaneous band over contrasts (result.ApoResult; drawn
                     # on the host only, so it has no device twin)
+P_HALF = 11         # half-sample inclusion bits of the RATE bootstrap (csrc/rate.hip)
 
 
 def philox4x32(c0, c1, c2, c3, k0, k1, rounds: int = 10):
@@ -110,6 +111,24 @@ def rademacher(seed: int, index, n_boot: int) -> np.ndarray:
         w = random_u32(seed, P_MULT, s, index)                        # (n, 4)
         bits = (w[:, :, None] >> shifts) & np.uint32(1)               # (n, 4, 32)
         out[:, s * 128:(s + 1) * 128] = bits.reshape(len(index), 128).astype(np.int8) * 2 - 1
+    return out[:, :n_boot]
+
+
+def half_sample(seed: int, index, n_boot: int) -> np.ndarray:
+    """Half-sample inclusion uint8 [n, n_boot] in {0, 1} of the rows with global ids
+    ``index``: replicate b of row i is the bit of :func:`rademacher`'s mapping -- bit b % 32
+    (LSB = 0) of word (b % 128) // 32 of ``random_u32(seed, P_HALF, b // 128, i)`` -- 1 when
+    the row is in replicate b's half sample (csrc/rate.hip reads the same bits). Every row is
+    in or out with probability 1/2 independently, keyed by its global id."""
+    index = np.asarray(index, dtype=np.uint64).reshape(-1)
+    n_boot = int(n_boot)
+    ns = -(-n_boot // 128)
+    out = np.empty((len(index), ns * 128), dtype=np.uint8)
+    shifts = np.arange(32, dtype=np.uint32)
+    for s in range(ns):                      # one stream at a time: bounded temporaries
+        w = random_u32(seed, P_HALF, s, index)                        # (n, 4)
+        bits = (w[:, :, None] >> shifts) & np.uint32(1)               # (n, 4, 32)
+        out[:, s * 128:(s + 1) * 128] = bits.reshape(len(index), 128).astype(np.uint8)
     return out[:, :n_boot]
 
 

@@ -604,6 +604,106 @@ def dml_irm_gate(Y, W, X, groups, folds=5, seed=1991, lambda_rule="min", clip=0.
     return res
 
 
+def _rate_grid(q):
+    g = np.arange(1, 11) / 10.0 if q is None else np.asarray(q, dtype=np.float64).reshape(-1)
+    if not 1 <= len(g) <= 64:
+        raise ValueError(f"q must hold between 1 and 64 points, got {len(g)}")
+    if not (np.isfinite(g).all() and g[0] > 0.0 and g[-1] <= 1.0 and np.all(np.diff(g) > 0)):
+        raise ValueError("q must be strictly increasing in (0, 1]")
+    return g
+
+
+def _rate_of_sample(psi, priority, thresholds):
+    """(AUTOC, QINI, TOC at the threshold priorities) of one sample, by its own tie groups:
+    the distinct priorities descending, the cumulative mean of psi down to each, and the
+    group-size-weighted averages of (cumulative mean - overall mean)."""
+    vals, inv, cnt = np.unique(-priority, return_inverse=True, return_counts=True)
+    n = len(psi)
+    csum = np.cumsum(np.bincount(inv, weights=psi, minlength=len(vals)))
+    k = np.cumsum(cnt)
+    theta = csum[-1] / n
+    gain = csum / k - theta
+    autoc = (cnt * gain).sum() / n
+    qini = (cnt * (k / n) * gain).sum() / n
+    # rows with priority >= threshold: the groups with -priority <= -threshold
+    upto = np.searchsorted(vals, -np.asarray(thresholds), side="right")
+    toc = np.where(upto > 0, gain[np.maximum(upto, 1) - 1], -theta)
+    return autoc, qini, toc
+
+
+def rate_from_scores(psi, priority, include, q=None, level=0.95):
+    """AUTOC, the Qini coefficient and the TOC curve of per-row scores under a priority rule
+    (higher = first, ties enter together), with half-sample bootstrap SEs, in float64 and
+    sample by sample: ``include`` [n, B] in {0, 1} picks each replicate's rows
+    (rng.half_sample). A replicate takes its rows, groups them by their own distinct
+    priorities, forms the cumulative means over those groups, and reads the TOC grid at the
+    full sample's threshold priorities -- the ceil(u n)-th largest. SE: the sd over the
+    replicates (ddof 1); crit: the ceil(level B)-th smallest of max_j |TOC_b - TOC| / SE over
+    the grid points with SE > 0. Returns a dict: autoc, qini, toc [Q], entered [Q], their
+    ``*_b`` replicates, ``*_se``, crit, ate, n, n_runs."""
+    from ..result import boot_rank
+    psi = np.asarray(psi, dtype=np.float64)
+    pr = np.asarray(priority, dtype=np.float64)
+    inc = np.asarray(include).astype(bool)
+    g = _rate_grid(q)
+    n, B = len(psi), inc.shape[1]
+    desc = np.sort(pr)[::-1]
+    kpos = np.clip(np.ceil(g * n - 1e-9).astype(np.int64), 1, n)
+    thr = desc[kpos - 1]
+    autoc, qini, toc = _rate_of_sample(psi, pr, thr)
+    ab, qb, tb = np.zeros(B), np.zeros(B), np.zeros((B, len(g)))
+    for b in range(B):
+        rows = inc[:, b]
+        ab[b], qb[b], tb[b] = _rate_of_sample(psi[rows], pr[rows], thr)
+    sd = lambda x: x.std(axis=0, ddof=1) if B > 1 else np.full(x.shape[1:], np.nan)
+    se_t = sd(tb)
+    live = se_t > 0
+    t = np.abs(tb[:, live] - toc[live]) / se_t[live]
+    crit = float(np.sort(t.max(axis=1))[boot_rank(level, B) - 1]) if live.any() else 0.0
+    return dict(autoc=autoc, qini=qini, toc=toc, autoc_b=ab, qini_b=qb, toc_b=tb,
+                autoc_se=float(sd(ab)), qini_se=float(sd(qb)), toc_se=se_t, crit=crit,
+                entered=np.array([(pr >= v).sum() for v in thr]), ate=psi.mean(), n=n,
+                n_runs=len(np.unique(pr)))
+
+
+def dml_irm_rate(Y, W, X, priority, q=None, subset=None, n_boot=200, level=0.95, folds=5,
+                 seed=1991, lambda_rule="min", clip=0.01, method="DML-IRM RATE (LASSO)",
+                 fold_ids=None, keep_boot=False, propensity="linear"):
+    """The RATE of a priority rule on the scores of dml_irm_lasso (the float64 twin of
+    estimators.rate.dml_irm_rate_lasso): the scores of every row, then rate_from_scores on
+    the evaluation rows ``subset`` with the half samples of rng.half_sample keyed by the
+    row number."""
+    from ..result import RateResult
+    Y, W, X = _arr(Y), _arr(W), _arr(X)
+    g = _rate_grid(q)
+    if int(n_boot) != n_boot or not 1 <= int(n_boot) <= 4096:
+        raise ValueError(f"n_boot must be an integer in [1, 4096], got {n_boot}")
+    if np.ndim(priority) == 0:
+        priority = X[:, int(priority)]
+    pr = _arr(priority).reshape(-1)
+    mask = np.ones(len(Y), dtype=bool) if subset is None else np.asarray(subset, dtype=bool)
+    if len(pr) != len(Y) or mask.shape != (len(Y),):
+        raise ValueError("priority and subset must have one entry per row")
+    if mask.sum() < 128:
+        raise ValueError(f"RATE needs at least 128 evaluation rows, got {int(mask.sum())}")
+    if not np.isfinite(pr[mask]).all():
+        raise ValueError("the priority must be finite on every evaluation row")
+    psi, _, _, _ = _irm_scores(Y, W, X, folds, seed, lambda_rule, clip, fold_ids, propensity)
+    rows = np.flatnonzero(mask)
+    r = rate_from_scores(psi[rows], pr[rows], rng.half_sample(seed, rows, int(n_boot)), g, level)
+    if r["entered"][0] < 64:
+        raise ValueError(f"the first grid point q = {g[0]} enters {r['entered'][0]} rows: at "
+                         "least 64 are needed")
+    fin = np.concatenate([[r["ate"], r["autoc"], r["autoc_se"], r["qini"], r["qini_se"],
+                           r["crit"], r["n"]], r["toc"], r["toc_se"]])
+    res = RateResult.make(method, g, r["entered"], fin, r["n"], r["n_runs"], int(n_boot), level)
+    if propensity != "linear":
+        res.diagnostics["propensity"] = propensity
+    if keep_boot:
+        res.boot = {k: r[k] for k in ("autoc_b", "qini_b", "toc_b")}
+    return res
+
+
 def bspline_design(x, knots, degree):
     """The B-spline design matrix [n, df] of the points x on a clamped knot vector, point by
     point from the textbook recursive Cox-de Boor definition (result.bspline_row)."""

@@ -936,6 +936,94 @@ class LateResult:
     to_json = json
 
 
+# ------------------------------------------------------------- RATE of a priority rule
+@dataclass
+class RateStat:
+    """One rank-weighted average (AUTOC or QINI): estimate, half-sample bootstrap SE, normal
+    interval at the result's level and the two-sided normal p-value of estimate = 0."""
+    estimate: float
+    se: float
+    lower_ci: float
+    upper_ci: float
+    p_value: float
+
+    @classmethod
+    def make(cls, estimate, se, z):
+        estimate, se = float(estimate), float(se)
+        p = math.erfc(abs(estimate) / se / math.sqrt(2.0)) if se > 0 else float("nan")
+        return cls(estimate, se, estimate - z * se, estimate + z * se, p)
+
+
+@dataclass
+class RateResult:
+    """The rank-weighted average treatment effect of a treatment-priority rule
+    (estimators/rate.py): AUTOC, the Qini coefficient and the TOC curve on the grid ``u``
+    with pointwise (normal) and uniform (bootstrap maximum) ``level`` bounds. ``toc`` holds
+    per-point lists: u, entered (rows treated at u, whole runs of ties), estimate, se,
+    lower_ci, upper_ci, lower_joint, upper_joint."""
+    method: str
+    autoc: RateStat
+    qini: RateStat
+    toc: dict
+    crit: float
+    ate: float                     # the mean score over the evaluation rows
+    n: int                         # evaluation rows
+    n_runs: int                    # distinct priorities among them
+    n_boot: int
+    level: float
+    diagnostics: dict = field(default_factory=dict)
+    boot: object = None            # keep_boot: the raw [n_boot + 1, 5 + 2 Q] walk buffer
+
+    @classmethod
+    def make(cls, method, u, entered, fin, n, n_runs, n_boot, level, **diag):
+        """``fin``: the flat vector of estimators.rate.rate_finalize."""
+        fin = [float(x) for x in fin]
+        Q = len(u)
+        z = normal_quantile(0.5 + 0.5 * level)
+        ate, a, sa, qn, sq, crit = fin[:6]
+        est, se = fin[7:7 + Q], fin[7 + Q:7 + 2 * Q]
+        toc = {"u": [float(x) for x in u], "entered": [int(x) for x in entered],
+               "estimate": est, "se": se,
+               "lower_ci": [e - z * s for e, s in zip(est, se)],
+               "upper_ci": [e + z * s for e, s in zip(est, se)],
+               "lower_joint": [e - crit * s for e, s in zip(est, se)],
+               "upper_joint": [e + crit * s for e, s in zip(est, se)]}
+        return cls(method, RateStat.make(a, sa, z), RateStat.make(qn, sq, z), toc, crit, ate,
+                   int(n), int(n_runs), int(n_boot), float(level), diag)
+
+    def rows(self):
+        t = self.toc
+        return [{k: t[k][j] for k in t} for j in range(len(t["u"]))]
+
+    def table(self) -> str:
+        lines = [f"{self.method}: n {self.n}, {self.n_runs} distinct priorities, ATE "
+                 f"{self.ate:.4f}, {self.n_boot} half samples, {self.level:.0%} bounds, "
+                 f"uniform crit {self.crit:.4f}",
+                 f"{'':>8s} {'estimate':>9s} {'SE':>9s} {'lower_ci':>9s} {'upper_ci':>9s} "
+                 f"{'p':>9s}"]
+        for name, r in (("AUTOC", self.autoc), ("QINI", self.qini)):
+            lines.append(f"{name:>8s} {r.estimate:9.4f} {r.se:9.4f} {r.lower_ci:9.4f} "
+                         f"{r.upper_ci:9.4f} {r.p_value:9.4g}")
+        lines.append(f"{'u':>8s} {'entered':>9s} {'TOC':>9s} {'SE':>9s} {'lower_ci':>9s} "
+                     f"{'upper_ci':>9s} {'lower_un':>9s} {'upper_un':>9s}")
+        for r in self.rows():
+            lines.append(f"{r['u']:8.3f} {r['entered']:9d} {r['estimate']:9.4f} {r['se']:9.4f} "
+                         f"{r['lower_ci']:9.4f} {r['upper_ci']:9.4f} {r['lower_joint']:9.4f} "
+                         f"{r['upper_joint']:9.4f}")
+        return "\n".join(lines)
+
+    def json(self) -> str:
+        keep = lambda d: {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v))
+                          for k, v in d.items()}
+        return json.dumps({"method": self.method, "autoc": asdict(self.autoc),
+                           "qini": asdict(self.qini), "toc": self.rows(), "crit": self.crit,
+                           "ate": self.ate, "n": self.n, "n_runs": self.n_runs,
+                           "n_boot": self.n_boot, "level": self.level,
+                           "diagnostics": keep(self.diagnostics)})
+
+    to_json = json
+
+
 # ------------------------------------------- potential outcomes of a multi-valued treatment
 APO_MIN_LEVELS, APO_MAX_LEVELS = 2, 8
 APO_LEVEL_MOMENTS = ("n_c", "n_clipped_c", "S 1{D=c}(y-g_c)^2", "S 1{D=c}/e_c")

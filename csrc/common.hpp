@@ -52,7 +52,7 @@ __host__ __device__ inline u32x4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c
 
 // purposes: keep in sync with rng.py
 enum : uint32_t { P_FOLD = 1, P_BOOT = 2, P_RF_BOOT = 3, P_RF_MTRY = 4, P_DGP = 5,
-                  P_SUBSAMPLE = 6, P_GBDT = 7, P_SAMPLE_ROWS = 8, P_MULT = 9 };
+                  P_SUBSAMPLE = 6, P_GBDT = 7, P_SAMPLE_ROWS = 8, P_MULT = 9, P_HALF = 11 };
 
 __host__ __device__ inline u32x4 rand4(uint64_t seed, uint32_t purpose, uint32_t stream,
                                        uint64_t index) {
